@@ -1,6 +1,7 @@
 """Headline benchmark: agent-env-steps/sec of the LPG meta-gradient step (BASELINE.json configs[1]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--env_mode tabular] [--agents_per_gpu 512]
+                    [--dump-outputs DIR] [--full [--no_cpu_baseline] [--workloads c3,c4]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,10 +18,20 @@ level_sampler.sample.  value = N_agents_total * W * T * K / seconds per step
 (inner-rollout agent-env-steps only; the eval rollout and eval_agent steps are
 extra work inside the timed step and are not counted).
 
-Rank 0 prints ONE JSON line.  The dominant kernel's roofline fraction is measured
-live with HIP events around its launches on the stream they run on.  The CPU
-baseline times the oracle restatement (oracle/, numpy rollout + torch-CPU float32
-autograd meta-gradient) on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps meta-steps (no HIP
+events in the streams) and prints the headline: metric, value, unit, ms_per_step, config, metrics.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left its caller as
+DIR/<name>.npy (float32, integer arrays as float64): the LPG parameters and Adam moments, the
+meta-gradient, the per-agent metrics and the agents' levels, tables, steps and env state (rank 0's
+agents; tables larger than DUMP_CAP_BYTES as a fixed, seeded sample of their rows).  Seeds are
+fixed, so the same arguments give the same inputs in every run.
+
+--full adds everything else to the line: a second pass of the same steps with per-kernel HIP
+events (`kernels`, the dominant kernel's roofline fraction, measured around its launches on the
+stream they run on), the CPU baseline (the oracle restatement: oracle/, numpy rollout + torch-CPU
+float32 autograd meta-gradient, on a bounded sample of the same workload; --no_cpu_baseline skips
+it), the GAE / PLR micro-benchmarks and, at N=1, the C3 / C4 workloads (--workloads).
 """
 from __future__ import annotations
 
@@ -109,10 +120,15 @@ def parse():
     ap.add_argument("--env_mode", default="tabular")
     ap.add_argument("--agents_per_gpu", type=int, default=512)
     ap.add_argument("--lifetime_conditioning", action="store_true")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel pass and rooflines, the CPU "
+                         "baselines, the micro-benchmarks and the --workloads")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--workloads", default="c3,c4",
-                    help="secondary BASELINE configs measured after the headline at N=1 (comma list of c3, c4; "
-                         "'none' to skip): each gets its own value, roofline and cpu_baseline under 'workloads'")
+                    help="with --full: secondary BASELINE configs measured after the headline at N=1 (comma list of "
+                         "c3, c4; 'none' to skip): each has its own value, roofline and cpu_baseline in 'workloads'")
     ap.add_argument("--cpu_agents", type=int, default=0, help="agents in the CPU sample (0 = auto-size to ~15 s)")
     ap.add_argument("--launcher_selftest", action="store_true",
                     help="test hook: run the multi-rank launch, barrier and max-over-ranks timing on gloo/CPU with "
@@ -615,6 +631,50 @@ def micro_plr(B: int = 4000, N: int = 512, reps: int = 50):
     return out
 
 
+DUMP_CAP_BYTES = 8 << 20     # per array; larger ones are written as a seeded sample of their rows
+DUMP_TOTAL_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, tr, metrics):
+    """What the last meta-step left its caller (make_lpg_train_step's 4-tuple: train state, agent states with their
+    value critics, metrics; plus the step's meta-gradient and the trainer's key), one DIR/<name>.npy each.  Float
+    tensors as float32, integer and key tensors as float64 (exact).  An array over DUMP_CAP_BYTES is written as the
+    rows (first axis) a RandomState(0) permutation picks, the same rows in every run."""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    ag = tr.agents
+    arrays = {"eta": tr.eta, "adam_m": tr.adam.m, "adam_v": tr.adam.v, "adam_count": torch.tensor([tr.adam.count]),
+              "meta_grad": tr.step_fn.grad, "rng": tr.rng,
+              "agents_levels": ag.levels, "agents_theta": ag.theta, "agents_phi": ag.phi, "agents_step": ag.step,
+              "agents_state": ag.state, "agents_vcrit": ag.vcrit, "agents_vstep": ag.vstep}
+
+    def flat(prefix, m):
+        for k, v in m.items():
+            if isinstance(v, dict):
+                flat(f"{prefix}{k}_", v)
+            else:
+                arrays[f"{prefix}{k}"] = v if torch.is_tensor(v) else torch.tensor([float(v)], dtype=torch.float64)
+    flat("metrics_", metrics)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        x = t.detach().cpu()
+        x = x.to(torch.float32 if x.dtype in (torch.float32, torch.float16, torch.bfloat16) else torch.float64)
+        x = x.numpy()
+        if x.ndim == 0:
+            x = x.reshape(1)
+        if x.nbytes > DUMP_CAP_BYTES and x.shape[0] > 1:
+            rows = max(1, DUMP_CAP_BYTES // (x.nbytes // x.shape[0]))
+            x = x[np.sort(np.random.RandomState(0).permutation(x.shape[0])[:rows])]
+        total += x.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_TOTAL_BYTES >> 20} MB at {name}")
+        np.save(d / f"{name}.npy", np.ascontiguousarray(x))
+
+
 def main():
     a = parse()
     ws = int(os.environ.get("WORLD_SIZE", "1"))
@@ -664,11 +724,57 @@ def main():
         return float(tmax), m
 
     dt, metrics = timed_pass(False)
-    dt_timed, _ = timed_pass(True)
-    ksum = step.timers.summary()
+    if a.dump_outputs and world.rank == 0:
+        dump_outputs(a.dump_outputs, tr, metrics)
     W, T, K = args.env_workers, args.train_rollout_len, args.num_agent_updates
     steps_per_meta = N_total * W * T * K
     value = steps_per_meta * a.steps / dt
+    out = {
+        "metric": "agent-env-steps/sec (inner rollout) at num_agents=512; meta-updates/sec",
+        "value": round(value, 1), "unit": "agent-env-steps/sec", "n_gpus": n_gpus, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+        "timing": "value and ms_per_step from an event-free pass",
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "mfma_precision": "f32-class: GRU recurrent products (forward carry, backward gate passes) on power-of-two-"
+                          "scaled fp16 pairs (3 fp16 MFMA products, pieces to 2^-22 relative), the weight-gradient "
+                          "reduction on block-floating-point fp16 pairs (3 products), the input k-step on the exact "
+                          "3-piece bf16 split (6 products), the n gate's input part on f32 MFMA; f32 accumulate",
+        "data": "synthetic (procedurally generated levels)",
+        "meta_updates_per_sec": round(a.steps / dt, 3),
+        "config": {"workload": f"C2 LPG meta-gradient env_mode={a.env_mode} num_agents={N_total} "
+                               f"num_mini_batches=1 W={W} T={T} K={K} score_function=random",
+                   "num_agents": N_total, "agents_per_gpu": a.agents_per_gpu, "env_workers": W,
+                   "train_rollout_len": T, "num_agent_updates": K, "parallelism": f"dp{n_gpus} (agent axis)"},
+        "metrics": {"lpg_agent_return": float(metrics["lpg_agent_return"].mean()),
+                    "lpg_loss": float(metrics["lpg_loss"].mean())},
+    }
+    if a.full:
+        headline_details(a, args, step, world, timed_pass, out)
+        wl = [w for w in a.workloads.split(",") if w and w != "none"]
+        if wl and n_gpus == 1:
+            del tr, step
+            torch.cuda.empty_cache()
+            out["workloads"] = {}
+            for w in wl:
+                fn = {"c3": workload_c3, "c4": workload_c4}[w]
+                t0w = time.perf_counter()
+                out["workloads"][w.upper()] = fn(a, not a.no_cpu_baseline)
+                out["workloads"][w.upper()]["wall_s"] = round(time.perf_counter() - t0w, 1)
+    if world.rank == 0:
+        print(json.dumps(out), flush=True)
+    if world.active:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def headline_details(a, args, step, world, timed_pass, out):
+    """--full: the headline's per-kernel pass (`kernels`, `roofline`, `roofline_secondary`), its CPU baseline and the
+    micro-benchmarks, added to the result line `out`."""
+    n_gpus = world.size
+    dt_timed, _ = timed_pass(True)
+    ksum = step.timers.summary()
+    W, T, K = args.env_workers, args.train_rollout_len, args.num_agent_updates
     F = 7 if a.lifetime_conditioning else 5
     R = a.agents_per_gpu * W
     kern = {}
@@ -723,28 +829,12 @@ def main():
                                 "traffic_note": "algorithmic 34 B + the draws path's key-chain / draws scratch (64 B) "
                                                 "per agent-env-step",
                                 "agent_env_steps_per_sec": round(rsteps / rsec, 1), "mean_ms": round(rsec * 1e3, 4)}
-    out = {
-        "metric": "agent-env-steps/sec (inner rollout) at num_agents=512; meta-updates/sec",
-        "value": round(value, 1), "unit": "agent-env-steps/sec", "n_gpus": n_gpus, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+    out.update({
         "ms_per_step_timed_pass": round(dt_timed / a.steps * 1e3, 3),
         "timing": "value and ms_per_step from an event-free pass; kernels and roofline from a second pass of the same "
                   "steps with per-kernel HIP events (ms_per_step_timed_pass)",
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "mfma_precision": "f32-class: GRU recurrent products (forward carry, backward gate passes) on power-of-two-"
-                          "scaled fp16 pairs (3 fp16 MFMA products, pieces to 2^-22 relative), the weight-gradient "
-                          "reduction on block-floating-point fp16 pairs (3 products), the input k-step on the exact "
-                          "3-piece bf16 split (6 products), the n gate's input part on f32 MFMA; f32 accumulate",
-        "data": "synthetic (procedurally generated levels)",
-        "meta_updates_per_sec": round(a.steps / dt, 3),
-        "config": {"workload": f"C2 LPG meta-gradient env_mode={a.env_mode} num_agents={N_total} "
-                               f"num_mini_batches=1 W={W} T={T} K={K} score_function=random",
-                   "num_agents": N_total, "agents_per_gpu": a.agents_per_gpu, "env_workers": W,
-                   "train_rollout_len": T, "num_agent_updates": K, "parallelism": f"dp{n_gpus} (agent axis)"},
         "roofline": roofline, "roofline_secondary": secondary, "kernels": kern,
-        "metrics": {"lpg_agent_return": float(metrics["lpg_agent_return"].mean()),
-                    "lpg_loss": float(metrics["lpg_loss"].mean())},
-    }
+    })
     if world.rank == 0:
         if not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.env_mode, a.lifetime_conditioning, a.cpu_agents)
@@ -752,22 +842,6 @@ def main():
             out["cpu_baseline"] = None
     if n_gpus == 1:
         out["micro"] = {"gae": micro_gae(), "plr_sampler": micro_plr()}
-    wl = [w for w in a.workloads.split(",") if w and w != "none"]
-    if wl and n_gpus == 1:
-        del tr, step
-        torch.cuda.empty_cache()
-        out["workloads"] = {}
-        for w in wl:
-            fn = {"c3": workload_c3, "c4": workload_c4}[w]
-            t0w = time.perf_counter()
-            out["workloads"][w.upper()] = fn(a, not a.no_cpu_baseline)
-            out["workloads"][w.upper()]["wall_s"] = round(time.perf_counter() - t0w, 1)
-    if world.rank == 0:
-        print(json.dumps(out), flush=True)
-    if world.active:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

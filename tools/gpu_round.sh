@@ -16,4 +16,4 @@ tail -2 "$O/gputest.log"
 timeout -k 10 120 python tools/bench_rollout.py --iters 3 > "$O/rollout.json" 2>&1; tail -1 "$O/rollout.json"
 timeout -k 10 120 python tools/bench_wgrad.py > "$O/wgrad.json" 2>&1; tail -1 "$O/wgrad.json"
 timeout -k 10 120 python tools/bench_gru.py --which both > "$O/gru.json" 2>&1; tail -1 "$O/gru.json"
-timeout -k 10 300 python bench.py --no_cpu_baseline > "$O/bench.json" 2>&1; tail -1 "$O/bench.json"
+timeout -k 10 300 python bench.py --full --no_cpu_baseline > "$O/bench.json" 2>&1; tail -1 "$O/bench.json"
