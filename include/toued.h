@@ -154,6 +154,17 @@ int toued_eval_returns(EnvSpec spec, const int* levels, const float* theta, int 
 /* CUs the non-table toued_eval_returns launch holds for n_workers eval workers (one workgroup each, TOUED_EVAL_BLOCK
  * workers per workgroup): what the caller reserves beside the weight-gradient reduction (toued_set_reserved_cus). */
 int toued_eval_returns_cus(int n_workers);
+/* GridWorld.optimal_return (gridworld.py:253-323) vmapped over n levels (RolloutWrapper.optimal_return,
+ * rollout.py:104-108): the exact finite-horizon optimal expected return of a tabular level by dynamic programming
+ * over (time, position, object existence), one workgroup per level with the value table in LDS (held as f64, rounded
+ * to f32 on output).  S = max_grid^2 * 2^n_max, state index pos + max_grid^2 * exists_mask.  v0 [n] =
+ * v_0(start_pos, all n_objs objects present); v_all (nullable) [n][max_rollout_len][S] = v_t(s), the reference's
+ * return_all=True after its flip: -inf at the invalid states (cell outside the grid or a wall, an unused object
+ * present), the whole row 0 for t >= max_steps_in_episode.  tabular == 0 is unsupported (-1; the reference raises
+ * NotImplementedError), as is a table that does not fit the kernel's LDS budget (every tabular mode fits);
+ * n == 0 and max_rollout_len == 0 succeed (v0 = 0). */
+int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int tabular, int max_rollout_len,
+                         float* v0, float* v_all, hipStream_t stream);
 
 
 /* ---- Level sampler (environments/level_sampler.py) ---- */

@@ -1,0 +1,234 @@
+// Exact optimal return of tabular GridWorld levels (environments/gridworld/gridworld.py:253-323, vmapped by
+// RolloutWrapper.optimal_return, environments/rollout.py:104-108) — HIP for gfx950.
+//
+// Finite-horizon dynamic programming over (time, position, object-existence): v_L = 0 and, for t = L-1 .. 0,
+//   q(s, a) = r + (1 - p_term) * E[v_{t+1}(pos1, e')],   v_t(s) = max_a q(s, a)
+// on the project's tabular state index s = pos + max_grid^2 * exists_mask (env_dev.h tab_index).
+//
+//   * One workgroup per level.  v_{t+1} and v_t are double-buffered in LDS as f64 (two tables of
+//     S = max_grid^2 * 2^n_max entries: 87 KB at the largest tabular mode), so the H accumulated backups stay far
+//     inside H * 2^-23 * max|v| of the float64 recursion; the outputs are rounded to f32 once.
+//   * Built once per level before the time loop: the (cell, action) -> next cell | objects-there table (the A2C
+//     chain's build_npt entries), the list of valid cells, the reward and 1 - p_term of every collected set, and the
+//     respawn weights P[absent][R] = prod over the absent objects of (R_i ? p_respawn_i : 1 - p_respawn_i) for every R
+//     inside `absent`.
+//   * Only valid states are enumerated (valid cell x subsets of the level's n_objs objects): a small level padded into
+//     a large mode's table costs what it contains.  Invalid states hold -inf in both buffers from the start and are
+//     never read by a valid state's backup (a move stays on valid cells, unused objects never appear), so no
+//     0 * (-inf) can form: a zero-weight outcome contributes an exact zero, as the reference's where(p > 0, v, 0).
+//   * Work items are ordered existence-mask major: the lanes of a wave share `absent`, so they run the same number of
+//     outcome terms and read neighbouring cells of one table slice; the masks are taken from the most absent objects to
+//     the fewest, so a thread's items (a block size apart) mix heavy and light states.
+//   * The outcome loop: per round two subsets' weights, read once for the five actions, and their ten values, read
+//     independently, feed ten f64 fmas (32-bit LDS indices, no per-term test).
+//   * One LDS-only barrier per time step; the only global traffic inside the loop is the optional v_all row store.
+//   * Only the count of unmasked steps matters (v_t is zero for t >= max_steps_in_episode): H = min(max_steps,
+//     max_rollout_len) backups give v_0, and the rows t >= max_steps of v_all are zero fills.
+#include "env_dev.h"
+
+namespace {
+
+constexpr size_t kOptretLdsMax = 150 * 1024;   // of the CU's 160 KB
+
+// dynamic LDS: f64 va[S], vb[S], pw[4^n_max + 1], rsum[2^n_max], keepw[2^n_max]; int lev[LEVEL_WORDS];
+// u16 nxt[G2 * 5]; u8 cells[G2], eord[2^n_max]
+__host__ __device__ inline size_t optret_lds_bytes(int G2, int n_max) {
+  const size_t S = (size_t)G2 << n_max;
+  size_t b = (2 * S + ((size_t)1 << (2 * n_max)) + 1 + ((size_t)2 << n_max)) * sizeof(double) +
+             LEVEL_WORDS * sizeof(int) + (size_t)G2 * 5 * sizeof(uint16_t) + (size_t)G2 + ((size_t)1 << n_max);
+  return (b + 15) & ~(size_t)15;
+}
+
+__global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, int n_max, int L,
+                                 float* __restrict__ v0, float* __restrict__ v_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int G2 = max_grid * max_grid;
+  const int S = G2 << n_max;
+  const int NE = 1 << n_max;
+  double* va = reinterpret_cast<double*>(smem);
+  double* vb = va + S;
+  double* pw = vb + S;
+  double* rsum = pw + NE * NE + 1;
+  double* keepw = rsum + NE;
+  int* lev = reinterpret_cast<int*>(keepw + NE);
+  uint16_t* nxt = reinterpret_cast<uint16_t*>(lev + LEVEL_WORDS);
+  uint8_t* cells = reinterpret_cast<uint8_t*>(nxt + G2 * 5);
+  uint8_t* eord = cells + G2;
+  __shared__ int s_ncell;
+
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int* glev = levels + (size_t)blockIdx.x * LEVEL_WORDS;
+  // the level record, with the fields that index tables held to the mode's static bounds
+  for (int i = tid; i < LEVEL_WORDS; i += nt) {
+    int w = glev[i];
+    if (i == L_GRID) w = w < 1 ? 1 : (w > max_grid ? max_grid : w);
+    if (i == L_NOBJS) w = w < 0 ? 0 : (w > n_max ? n_max : w);
+    if (i == L_START) w = w < 0 ? 0 : (w >= G2 ? G2 - 1 : w);
+    lev[i] = w;
+  }
+  __syncthreads();
+  const int g = lev[L_GRID], g2 = g * g;
+  const int nobj = lev[L_NOBJS], used = (1 << nobj) - 1, ne = 1 << nobj;
+  const int max_steps = lev[L_MAX_STEPS];
+  const int H = max_steps < L ? (max_steps < 0 ? 0 : max_steps) : L;
+  const float ninf = -__builtin_inff();
+
+  // (cell, action) -> next cell | (objects placed there) << 8, for the level's valid cells
+  for (int c = tid; c < G2 * 5; c += nt) {
+    const int pos = c / 5, a = c - pos * 5;
+    uint16_t e = 0;
+    if (pos < g2 && !wall_at((const int*)lev, pos)) {
+      const int p1 = next_pos((const int*)lev, pos, a);
+      int m = 0;
+      for (int o = 0; o < nobj; ++o)
+        if (lev[L_STATIC + o] == p1) m |= 1 << o;
+      e = (uint16_t)(p1 | (m << 8));
+    }
+    nxt[c] = e;
+  }
+  // reward and 1 - p_term of collecting the objects c (c inside used)
+  for (int c = tid; c < ne; c += nt) {
+    double rs = 0.0, pt = 0.0;
+    for (int o = 0; o < nobj; ++o)
+      if ((c >> o) & 1) {
+        rs += (double)__int_as_float(lev[L_REW + o]);
+        pt += (double)__int_as_float(lev[L_PTERM + o]);
+      }
+    rsum[c] = rs;
+    keepw[c] = 1.0 - pt;
+  }
+  // respawn weights: pw[absent * NE + R], R inside absent inside used
+  for (int i = tid; i < NE * NE; i += nt) {
+    const int A = i >> n_max, R = i & (NE - 1);
+    double p = 0.0;
+    if (!(R & ~A) && !(A & ~used)) {
+      p = 1.0;
+      for (int o = 0; o < nobj; ++o)
+        if ((A >> o) & 1) {
+          const double pr = (double)__int_as_float(lev[L_PRESP + o]);
+          p *= ((R >> o) & 1) ? pr : 1.0 - pr;
+        }
+    }
+    pw[i] = p;
+  }
+  if (tid == 0) pw[NE * NE] = 0.0;
+  if (tid == 0) {
+    int n = 0;
+    for (int pos = 0; pos < g2; ++pos)
+      if (!wall_at((const int*)lev, pos)) cells[n++] = (uint8_t)pos;
+    s_ncell = n;
+  }
+  // the level's existence masks by ascending count of present objects, i.e. from the most outcome terms (2^absent) to
+  // the fewest: a thread's work items, a block size apart in this order, then mix heavy and light states
+  if (tid == 64 % nt) {
+    int n = 0;
+    for (int pc = 0; pc <= nobj; ++pc)
+      for (int e = 0; e < ne; ++e)
+        if (__builtin_popcount(e) == pc) eord[n++] = (uint8_t)e;
+  }
+  // both tables: -inf at the invalid states for good, v_H = 0 at the valid ones
+  for (int s = tid; s < S; s += nt) {
+    const int pos = s % G2, e = s / G2;
+    const bool valid = pos < g2 && !wall_at((const int*)lev, pos) && !(e & ~used);
+    va[s] = vb[s] = valid ? 0.0 : (double)ninf;
+  }
+  // rows t >= max_steps of v_all are zero, invalid states included
+  if (v_all != nullptr) {
+    float* rows = v_all + ((size_t)blockIdx.x * L + H) * S;
+    const size_t nz = (size_t)(L - H) * S;
+    for (size_t i = tid; i < nz; i += nt) rows[i] = 0.0f;
+  }
+  __syncthreads();
+
+  const int ncell = s_ncell;
+  const int nwork = ncell * ne;
+  int curo = 0;    // v_t, written: table va (offset 0) or vb (offset S) of the 2S-entry array
+  int nxo = S;     // v_{t+1}, read
+  for (int t = H - 1; t >= 0; --t) {
+    for (int w = tid; w < nwork; w += nt) {
+      const int ei = w / ncell;
+      const int e = eord[ei], pos = cells[w - ei * ncell];
+      const int absent = used & ~e;
+      const double* pwa = pw + absent * NE;
+      int base[5];
+      double r[5], keep[5], ev[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        const uint32_t en = nxt[pos * 5 + a];
+        const int c = (int)(en >> 8) & e;
+        base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~c);
+        r[a] = rsum[c];
+        keep[a] = keepw[c];
+        ev[a] = 0.0;
+      }
+      // the subsets R of `absent`, two per round: one weight read serves the five actions, and the ten value reads
+      // of a round are independent.  Every value read is a valid state's (finite), so a zero weight gives a zero
+      // term without a test; a second subset that does not exist reads subset 0 with weight 0.
+      int R0 = 0;
+      do {
+        const int R1 = (R0 - absent) & absent;
+        const double p0 = pwa[R0];
+        const double p1 = pw[R1 != 0 ? absent * NE + R1 : NE * NE];   // pw[NE * NE] = 0
+        const int o0 = G2 * R0, o1 = G2 * R1;
+        double x0[5], x1[5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) { x0[a] = va[base[a] + o0]; x1[a] = va[base[a] + o1]; }
+        __builtin_amdgcn_sched_barrier(0);   // all twelve reads in flight before the first fma waits
+#pragma unroll
+        for (int a = 0; a < 5; ++a) ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
+        R0 = R1 != 0 ? (R1 - absent) & absent : 0;
+      } while (R0 != 0);
+      double best = (double)ninf;
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        const double q = r[a] + ev[a] * keep[a];
+        best = q > best ? q : best;
+      }
+      va[curo + pos + G2 * e] = best;
+    }
+    lds_barrier();
+    if (v_all != nullptr) {
+      float* row = v_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) row[s] = (float)va[curo + s];
+    }
+    const int sw = curo; curo = nxo; nxo = sw;
+  }
+  // table nxo now holds v_0 (v0 is 0 when H == 0, whatever the start cell)
+  if (tid == 0) v0[blockIdx.x] = H > 0 ? (float)va[nxo + lev[L_START] + G2 * used] : 0.0f;
+}
+
+}  // namespace
+
+extern "C" {
+
+int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int tabular, int max_rollout_len,
+                         float* v0, float* v_all, hipStream_t stream) {
+  TOUED_REQUIRE(tabular != 0, "toued_optimal_return: non-tabular environments are unsupported (the reference "
+                "raises NotImplementedError)");
+  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_optimal_return: n=%d max_rollout_len=%d must be >= 0", n,
+                max_rollout_len);
+  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_optimal_return: max_grid=%d outside [1, 16]", max_grid);
+  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_optimal_return: n_max=%d outside [0, %d]", n_max,
+                TOUED_MAX_OBJS);
+  const int G2 = max_grid * max_grid;
+  const size_t lds = optret_lds_bytes(G2, n_max);
+  TOUED_REQUIRE(lds <= kOptretLdsMax, "toued_optimal_return: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)",
+                max_grid, n_max, lds, kOptretLdsMax);
+  if (n == 0) return 0;
+  static bool attr_set = false;
+  if (!attr_set) {
+    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_optimal_return),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
+                  "toued_optimal_return: cannot raise the dynamic LDS limit");
+    attr_set = true;
+  }
+  // block size from the table size: one state per thread up to 1024 threads
+  const int S = G2 << n_max;
+  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
+  hipLaunchKernelGGL(k_optimal_return, dim3(n), dim3(block), lds, stream, levels, max_grid, n_max, max_rollout_len,
+                     v0, v_all);
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

@@ -3,8 +3,10 @@
 ``LevelSampler(args)`` mirrors the reference: ``initialize_buffer``,
 ``initial_sample``, ``sample``, ``rollout_manager``, ``max_lifetime``.
 Score functions: ``random`` (domain randomisation), ``frozen`` (uniform replay
-of a fixed buffer) and ``alg_regret`` (PLR with the A2C antagonist's
-algorithmic regret, GROOVE).  All state is device-resident; per-agent work is
+of a fixed buffer), ``alg_regret`` (PLR with the A2C antagonist's
+algorithmic regret, GROOVE) and ``optimal_regret`` (PLR with the true regret
+against the level's exact optimal return; tabular modes, not in the reference).
+All state is device-resident; per-agent work is
 computed for the whole batch and masked by ``terminated`` exactly like the
 reference's vmapped ``jnp.where`` (the masked-out work has no observable effect).
 """
@@ -22,7 +24,7 @@ from .agents import (DENSE0_HASH, AgentBatch, AgentHyperparams, create_agents, c
 from .env import L_BUFID, L_LIFETIME, LevelGenerator, get_env_spec
 from .rollout import RolloutWrapper
 
-SCORE_FUNCTIONS = ["random", "frozen", "alg_regret"]
+SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "optimal_regret"]
 SCORE_TRANSFORMS = ["proportional", "rank"]
 
 
@@ -65,6 +67,9 @@ class LevelSampler:
         self.spec, self.max_rollout_len, self.max_lifetime = get_env_spec(self.env_mode)
         self.rollout_manager = RolloutWrapper(self.env_mode, args.train_rollout_len, self.max_rollout_len,
                                               args.env_workers)
+        if args.score_function == "optimal_regret" and not self.spec.tabular:
+            raise ValueError(f"Level score function optimal_regret needs a tabular environment mode: the optimal "
+                             f"return is not defined for {self.env_mode}")
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
         if args.score_function not in SCORE_FUNCTIONS:

@@ -9,6 +9,9 @@
   4. toued_plr_sample: replay ids (rank or proportional), random new ids, the bernoulli/permutation
      selection (:203-227); ``active[new_ids] = True`` (:232-234).
 
+With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
+exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
+
 Multi-GPU: the buffer is replicated on every rank and updated identically; each rank scores
 its own agents and the per-agent (term, score, buffer id) vectors are all-gathered, so every
 rank runs the same single-workgroup sampler kernel on the same inputs.
@@ -92,6 +95,26 @@ def algorithmic_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_th
     return r_a2c - r_lpg
 
 
+def optimal_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor) -> torch.Tensor:
+    """The true regret of n LPG agents on tabular levels: V*(level) - eval(LPG), with V* the exact optimal return over
+    the eval rollout length (RolloutWrapper.optimal_return) in place of the trained antagonist's return.  Same
+    signature and return as ``algorithmic_regret``, and the LPG agent is evaluated with the same key (the splits of
+    level_sampler.py:293-329), so its return is bit-identical between the two scores.  An extension: the reference's
+    LevelSampler has no such score function."""
+    n = keys.shape[0]
+    if n == 0:
+        return torch.zeros(0, device=keys.device)
+    ro = sampler.rollout_manager
+    rng, _ = _split2(keys)
+    rng, _ = _split2(rng)
+    lpg_rng, _ = _split2(rng)
+    return ro.optimal_return(levels, ro.eval_rollout_len) - eval_agent(ro, lpg_rng, levels, lpg_theta,
+                                                                      sampler.env_workers)
+
+
+REGRET_FUNCTIONS = {"alg_regret": algorithmic_regret, "optimal_regret": optimal_regret}
+
+
 # the regret round's eval draws ([eval_len][2n * W][4] u32, plus as much key-chain scratch) are made ahead when they fit
 EVAL_DRAWS_MAX_BYTES = 4 << 30
 
@@ -137,13 +160,14 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     if sl is not None:
         keys = keys[sl[0]:sl[1]].contiguous()
     score = torch.zeros(agents.n, dtype=torch.float32, device=dev)
+    regret = REGRET_FUNCTIONS[sampler.score_function]
     if sampler.regret_all_agents:
-        score = algorithmic_regret(sampler, keys, agents.levels, agents.theta)
+        score = regret(sampler, keys, agents.levels, agents.theta)
     else:
         sel = term.nonzero().flatten()
         if sel.numel():
-            score[sel] = algorithmic_regret(sampler, keys[sel].contiguous(), agents.levels[sel].contiguous(),
-                                            agents.theta[sel].contiguous())
+            score[sel] = regret(sampler, keys[sel].contiguous(), agents.levels[sel].contiguous(),
+                                agents.theta[sel].contiguous())
     nan_checker().check("regret_scores", score)
     old_ids = agents.levels[:, L_BUFID].contiguous()
     if world is not None and world.active:

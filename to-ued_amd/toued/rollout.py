@@ -192,6 +192,26 @@ class RolloutWrapper:
                   N, n // N, self.eval_rollout_len, _lib.ptr(draws), _lib.ptr(cum), _lib.stream_ptr())
         return cum
 
+    def optimal_return(self, levels: torch.Tensor, max_rollout_len: int, return_all: bool = False) -> torch.Tensor:
+        """rollout.py:104-108: vmap(GridWorld.optimal_return) (gridworld.py:253-323), the exact optimal expected
+        return of tabular levels over ``max_rollout_len`` steps (toued_optimal_return, no host synchronisation).
+
+        levels int32 [n, 80] -> f32 [n]: v_0 at the start state.  ``return_all``: f32 [n, max_rollout_len, S] with
+        S = obs_dim - 1 table states (the reference's shape: the observation's last entry is the time feature, not
+        a state), v_t of every tabular state, -inf at the invalid ones and 0 from max_steps_in_episode on.  A single
+        level [80] returns a 0-d tensor, or [max_rollout_len, S].  Non-tabular modes raise NotImplementedError."""
+        if not self.spec.tabular:
+            raise NotImplementedError("Optimal return not implemented for non-tabular environments.")
+        if levels.dim() == 1:
+            return self.optimal_return(levels.view(1, -1), max_rollout_len, return_all)[0]
+        n, L = levels.shape[0], int(max_rollout_len)
+        S = self.obs_dim - 1
+        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
+        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
+        _lib.call("toued_optimal_return", _lib.ptr(levels), n, self.spec.max_grid_size, self.spec.max_n_objs,
+                  int(self.spec.tabular), L, _lib.ptr(v0), _lib.ptr(v_all), _lib.stream_ptr())
+        return v_all if return_all else v0
+
     def eval_returns(self, agent_keys: torch.Tensor, theta: torch.Tensor, levels: torch.Tensor,
                      state: torch.Tensor) -> torch.Tensor:
         """batch_rollout(..., eval=True) when only cum_return is consumed (eval_agent): returns-only
