@@ -141,10 +141,40 @@ def test_track_best_on_device_matches_evosax_rule():
         np.testing.assert_array_equal(es.best_member.cpu().numpy(), host_member, err_msg=str(g))
 
 
+# max_grad_norm of the "clipped" ES cases: inside the spread of the candidates' gradient norms at these inputs (at the
+# mode's own 0.5 no candidate clips), so toued_agent_update's clipped in-place branch runs beside its unclipped one
+_ES_CLIP_NORM = 0.017
+
+
+def _es_clip_census(gstat, max_norm):
+    """ESTrainStep.gstat [C, 4] (the last update's norms and applied flag) -> counts per branch, printed."""
+    g = gstat.cpu().numpy()
+    ap = g[:, 2] > 0.5
+    out = {"actor_clipped": int((ap & (g[:, 0] >= max_norm)).sum()),
+           "actor_unclipped": int((ap & (g[:, 0] < max_norm)).sum()),
+           "critic_clipped": int((ap & (g[:, 1] >= max_norm)).sum()),
+           "critic_unclipped": int((ap & (g[:, 1] < max_norm)).sum()), "not_applied": int((~ap).sum())}
+    print(f"max_grad_norm {max_norm}: |G_theta| {g[:, 0]}, |G_phi| {g[:, 1]}, applied {g[:, 2]}: {out}")
+    return out
+
+
 def test_es_fused_agent_update_bitexact():
     """toued_agent_update (gradient + clip + SGD in place, the ES default) against toued_agent_grad + toued_agent_apply
     into ping-pong tables: three agent updates per candidate, lifetime 2 on one agent (a discarded update), the ES
     step's outputs bit-identical -- winners' tables, steps, env state, metrics, fitness and the new search mean."""
+    _es_fused_agent_update_case(None)
+
+
+def test_es_fused_agent_update_bitexact_clipped():
+    """The same with max_grad_norm lowered into the candidates' gradient norms: the clipped in-place branch of
+    toued_agent_update ((g / |G|) * max_norm per element) bit-identical to toued_agent_grad + toued_agent_apply,
+    with clipped, unclipped and discarded updates in the last launch (asserted from gstat)."""
+    census = _es_fused_agent_update_case(_ES_CLIP_NORM)
+    assert census["actor_clipped"] + census["critic_clipped"] > 0, census
+    assert census["actor_unclipped"] + census["critic_unclipped"] > 0 and census["not_applied"] > 0, census
+
+
+def _es_fused_agent_update_case(max_grad_norm):
     from toued import prng
     from toued.env import L_LIFETIME
     from toued.es import ESTrainStep
@@ -166,6 +196,9 @@ def test_es_fused_agent_update_bitexact():
                            num_agent_updates=3)
         assert step.fused_update                      # the default where the sizes fit
         step.fused_update = fused
+        assert step.mn == smp.agent_hypers.max_grad_norm == 0.5
+        if max_grad_norm is not None:
+            step.mn = max_grad_norm
         step.es.mean.copy_(torch.from_numpy(np.random.RandomState(5).randn(step.es.nd).astype(np.float32) * 0.05))
         m = step(dk(jr.PRNGKey(7)), agents)
         torch.cuda.synchronize()
@@ -180,6 +213,7 @@ def test_es_fused_agent_update_bitexact():
     assert outs[0][7].keys() == outs[1][7].keys()
     for k in outs[0][7]:
         assert torch.equal(outs[0][7][k], outs[1][7][k]), k
+    return _es_clip_census(outs[1][6], 0.5 if max_grad_norm is None else max_grad_norm)
 
 
 def _flat(m, pre=""):
@@ -195,6 +229,18 @@ def _flat(m, pre=""):
 def test_es_step_k1_matches_oracle():
     """K = 1: the device's one trajectory per candidate is fed to the oracle update (the K = 3 test below also
     regenerates the rollouts)."""
+    _es_step_k1_case(None)
+
+
+def test_es_step_k1_matches_oracle_clipped():
+    """The same with max_grad_norm lowered into the candidates' gradient norms: toued_agent_update's clipped branch
+    within the same 2e-5 of ometa.lpg_agent_step; the branch every candidate's table took is the one the oracle's
+    float64 norm gives (each norm at least 2 % away from max_grad_norm), and some table clips."""
+    census = _es_step_k1_case(_ES_CLIP_NORM)
+    assert census["actor_clipped"] > 0 and census["actor_unclipped"] > 0 and census["critic_clipped"] > 0, census
+
+
+def _es_step_k1_case(max_grad_norm):
     from toued import prng
     from toued.es import ESTrainStep
     from toued.level_sampler import LevelSampler
@@ -210,6 +256,9 @@ def test_es_step_k1_matches_oracle():
     from toued.lpg import LPGLayout
     eta0 = torch.zeros(LPGLayout(7).size, device="cuda")
     step = ESTrainStep(args, smp, N, eta0, "cuda", None, num_agent_updates=1)
+    assert step.mn == smp.agent_hypers.max_grad_norm == 0.5
+    mn = 0.5 if max_grad_norm is None else max_grad_norm
+    step.mn = mn
     # non-zero search mean so the candidate LPGs produce non-trivial targets
     step.es.mean.copy_(torch.from_numpy(np.random.RandomState(5).randn(step.es.nd).astype(np.float32) * 0.05))
     th0, ph0 = agents.theta.cpu().numpy(), agents.phi.cpu().numpy()
@@ -224,21 +273,42 @@ def test_es_step_k1_matches_oracle():
     tr = step.tr
     idx, tm, act = tr.obs_idx.cpu().numpy(), tr.obs_time.cpu().numpy(), tr.action.cpu().numpy()
     rew, dn = tr.reward.cpu().numpy(), tr.done.cpu().numpy()
-    hyp = ometa.Hypers(lifetime_conditioning=True)
+    hyp = ometa.Hypers(lifetime_conditioning=True, max_grad_norm=mn)
     theta_dev = step.theta[step.cur].cpu().numpy()     # the candidates' tables after the update
+    phi_dev = step.phi[step.cur].cpu().numpy()
+    gstat = step.gstat.cpu().numpy()
+    census = _es_clip_census(step.gstat, mn)
     from oracle.levels import L_LIFETIME
+    gnorms = []          # the oracle's float64 |G_theta|, |G_phi| per candidate, in front of its two clips
+    clip_sgd = ometa.clip_sgd
+
+    def recording_clip_sgd(params, grad, lr, max_norm):
+        gnorms.append(float(torch.sqrt(torch.sum(grad.detach() ** 2))))
+        return clip_sgd(params, grad, lr, max_norm)
     for c in range(C):
         a = c // 2
         traj = {"idx": idx[c].T.copy(), "time": tm[c].T.copy(), "action": act[c].T.astype(np.int64),
                 "reward": rew[c].T.copy(), "done": dn[c].T.astype(bool)}
         eta_c = torch.tensor(x[c], dtype=torch.float64)
-        th1, ph1, s1, _, _ = ometa.lpg_agent_step(torch.tensor(th0[a], dtype=torch.float64, requires_grad=True),
-                                                  torch.tensor(ph0[a], dtype=torch.float64, requires_grad=True),
-                                                  int(step_np[a]),
-                                                  int(lev[a, L_LIFETIME]), eta_c, traj, hyp)
+        ometa.clip_sgd = recording_clip_sgd
+        try:
+            th1, ph1, s1, _, _ = ometa.lpg_agent_step(torch.tensor(th0[a], dtype=torch.float64, requires_grad=True),
+                                                      torch.tensor(ph0[a], dtype=torch.float64, requires_grad=True),
+                                                      int(step_np[a]),
+                                                      int(lev[a, L_LIFETIME]), eta_c, traj, hyp)
+        finally:
+            ometa.clip_sgd = clip_sgd
         d_ref = th1.detach().numpy() - th0[a]
         d_dev = theta_dev[c].astype(np.float64) - th0[a]
         assert np.linalg.norm(d_dev - d_ref) <= 2e-5 * np.linalg.norm(d_ref) + 1e-7, c
+        d_ref = ph1.detach().numpy() - ph0[a]
+        d_dev = phi_dev[c].astype(np.float64) - ph0[a]
+        assert np.linalg.norm(d_dev - d_ref) <= 2e-5 * np.linalg.norm(d_ref) + 1e-7, c
+        # the branch of each table (actor, critic), from the oracle's float64 norms
+        for t in range(2):
+            gn = gnorms[2 * c + t]
+            assert abs(gn / mn - 1.0) >= 0.02 and (gn >= mn) == (gstat[c, t] >= mn), (c, t, gn, gstat[c, t])
+    assert len(gnorms) == 2 * C
     # fitness = eval_agent(rng_c) on the device-trained actor
     ck = jr.split(jr.split(ks[0], 2)[1], 2 * N)
     fit_keys = jr.split(ck, 2)[:, 0]
@@ -255,6 +325,7 @@ def test_es_step_k1_matches_oracle():
     winners = np.where(fg, np.arange(N) * 2, np.arange(N) * 2 + 1)
     assert np.array_equal(agents.theta.cpu().numpy(), theta_dev[winners])
     assert float(m["fitness"]["max"]) == pytest.approx(float(f.max()))
+    return census
 
 
 def certify_es_step(args, smp, step, rng, pre, metrics, p_lv, chained=False):

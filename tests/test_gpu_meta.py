@@ -15,6 +15,7 @@ parameters after K updates rtol/atol 2e-5; metrics rtol 2e-5; meta-gradient
 relative L2 error < 1e-5; GRU forward outputs and saves 5e-6 abs; GRU backward
 gradients 1e-5 relative L2.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -30,7 +31,7 @@ from oracle import levels as olv
 pytestmark = pytest.mark.gpu
 
 
-def _setup(mode, N, W, T, K, lifetime_conditioning=False, seed=0):
+def _setup(mode, N, W, T, K, lifetime_conditioning=False, seed=0, max_grad_norm=0.5):
     from toued import prng
     from toued.agents import AgentBatch, create_agents, create_value_critics
     from toued.env import LevelGenerator
@@ -51,7 +52,7 @@ def _setup(mode, N, W, T, K, lifetime_conditioning=False, seed=0):
     (_, _), state = ro.batch_reset(dk(jr.split(jr.PRNGKey(seed + 3), N)), levels)
     agents = AgentBatch(levels, theta, phi, torch.zeros(N, dtype=torch.int32, device="cuda"), state, vcrit,
                         torch.zeros(N, dtype=torch.int32, device="cuda"))
-    hyp = LpgHyperparams(num_agent_updates=K)
+    hyp = LpgHyperparams(num_agent_updates=K, max_grad_norm=max_grad_norm)
     step = MetaGradStep(ro, N, hyp, lifetime_conditioning)
     F = 7 if lifetime_conditioning else 5
     eta = init_lpg_params(seed + 4, F)
@@ -59,37 +60,70 @@ def _setup(mode, N, W, T, K, lifetime_conditioning=False, seed=0):
     return agents, step, eta, adam, hyp, D
 
 
-@pytest.mark.parametrize("mode,lc", [("dense", False), ("tabular", True), ("mazes", False), ("all_vrandlife", True)])
-def test_meta_step_matches_oracle(mode, lc):
-    N, W, T, K = 3, 64, 20, 3
-    agents, step, eta, adam, hyp, D = _setup(mode, N, W, T, K, lc)
-    theta0 = agents.theta.cpu().numpy()
-    phi0 = agents.phi.cpu().numpy()
-    vcrit = agents.vcrit.cpu().numpy()
-    state0 = agents.state.cpu().numpy()
-    eta0 = eta.clone()
-    lv = agents.levels.cpu().numpy()
-    rng = torch.tensor([0, 77], dtype=torch.int32, device="cuda")
+def _run_checked_step(agents, step, eta, adam, rng_words=(0, 77)):
+    """One meta-step on `agents`; everything the oracle comparison needs, as host arrays: the agents' tables, steps,
+    env state and levels from before the step, the step's trajectories, theta_k / phi_k, gstat, metrics and the
+    (agent-mean, float64) meta-gradient."""
+    N = agents.theta.shape[0]
+    run = {"theta0": agents.theta.cpu().numpy(), "phi0": agents.phi.cpu().numpy(),
+           "vcrit": agents.vcrit.cpu().numpy(), "state0": agents.state.cpu().numpy(),
+           "step0": agents.step.cpu().numpy(), "eta0": eta.cpu().numpy().astype(np.float64),
+           "levels": agents.levels.cpu().numpy(), "rng": tuple(rng_words)}
+    rng = torch.tensor(list(rng_words), dtype=torch.int32, device="cuda")
     metrics = step(rng, eta, adam, agents)
     torch.cuda.synchronize()
-    g_gpu = step.grad.cpu().double().numpy() / N   # f64: a float32 norm alone is off by ~1e-7 (the cosine bound is 1e-9)
+    # f64: a float32 norm alone is off by ~1e-7 (the cosine bound is 1e-9)
+    run["grad"] = step.grad.cpu().double().numpy() / N
     tr = step.traj
-    idx = tr.obs_idx.cpu().numpy()
-    tm = tr.obs_time.cpu().numpy()
-    act = tr.action.cpu().numpy()
-    rew = tr.reward.cpu().numpy()
-    dn = tr.done.cpu().numpy()
+    run["traj"] = {"idx": tr.obs_idx.cpu().numpy(), "time": tr.obs_time.cpu().numpy(),
+                   "action": tr.action.cpu().numpy(), "reward": tr.reward.cpu().numpy(), "done": tr.done.cpu().numpy()}
     th_h = step.theta_h.cpu().numpy()
-    th_h[0] = theta0          # slot 0 is the agents' own table storage: after the step it holds theta_K
+    th_h[0] = run["theta0"]   # slot 0 is the agents' own table storage: after the step it holds theta_K
+    ph_h = step.phi_h.cpu().numpy()
+    ph_h[0] = run["phi0"]
+    run["theta_h"], run["phi_h"] = th_h, ph_h
+    run["gstat"] = step.gstat.cpu().numpy()
+    run["theta"], run["phi"] = agents.theta.cpu().numpy(), agents.phi.cpu().numpy()
+    run["step"] = agents.step.cpu().numpy()
+    run["metrics"] = {"lpg_loss": metrics["lpg_loss"].cpu().numpy(),
+                      "lpg_agent": {k: v.cpu().numpy() for k, v in metrics["lpg_agent"].items()}}
+    return run
+
+
+@contextlib.contextmanager
+def _recorded_clip_norms():
+    """Records (table columns, float64 gradient norm) of every ometa.clip_sgd call made inside the block, in call
+    order: the oracle's own view of which clip branch each update takes."""
+    seen = []
+    clip_sgd = ometa.clip_sgd
+
+    def recording_clip_sgd(params, grad, lr, max_norm):
+        seen.append((int(params.shape[-1]), float(torch.sqrt(torch.sum(grad.detach().double() ** 2)))))
+        return clip_sgd(params, grad, lr, max_norm)
+    ometa.clip_sgd = recording_clip_sgd
+    try:
+        yield seen
+    finally:
+        ometa.clip_sgd = clip_sgd
+
+
+def _oracle_of_run(mode, run, K, T, ohyp, seed=0, dtype=torch.float64):
+    """The float64 oracle on the trajectories of `run`: every rollout k = 0..K first regenerated bit-exactly by the
+    numpy rollout driven by the GPU's theta_k, then ometa.meta_gradient.  Returns (g_ref, aux, norms) with norms
+    [K][N][2] the oracle's own gradient norms |G_theta|, |G_phi| in front of each clip (ometa.clip_sgd)."""
+    tj = run["traj"]
+    idx, tm, act, rew, dn = tj["idx"], tj["time"], tj["action"], tj["reward"], tj["done"]
+    N = run["theta0"].shape[0]
+    lv = run["levels"]
     # ---- trajectories: every rollout k = 0..K bit-exact vs the numpy rollout driven by the GPU's theta_k
     spec = olv.env_spec(mode)
-    keys = jr.split(jr.PRNGKey(0), N)
+    keys = jr.split(jr.PRNGKey(seed), N)
     p, lt = olv.reset_env_params(keys, mode)
     from test_gpu_env import _state_np
-    ost = _state_np(torch.from_numpy(state0), spec)
+    ost = _state_np(torch.from_numpy(run["state0"]), spec)
     # meta/train.py:41 (r0, t) = split(rng_a); lpg_agent.py:107 (t, roll_k) = split(t) per update k;
     # meta/train.py:47 (r0, roll_eval) = split(r0)
-    ka = jr.split(np.array([0, 77], np.uint32), N)
+    ka = jr.split(np.array(run["rng"], np.uint32), N)
     r0t = jr.split(ka, 2)
     r0, tk = r0t[:, 0], r0t[:, 1]
     for k in range(K + 1):
@@ -98,7 +132,7 @@ def test_meta_step_matches_oracle(mode, lc):
             tk, rk = s2[:, 0], s2[:, 1]
         else:
             rk = jr.split(r0, 2)[:, 1]
-        otr, ost, _ = oro.batch_rollout(spec, rk, th_h[k], p, ost, T)
+        otr, ost, _ = oro.batch_rollout(spec, rk, run["theta_h"][k], p, ost, T)
         for name, got in (("idx", idx), ("time", tm), ("action", act), ("reward", rew), ("done", dn)):
             np.testing.assert_array_equal(got[k], otr[name].transpose(0, 2, 1).astype(got.dtype),
                                           err_msg=f"rollout {k} {name}")
@@ -108,23 +142,44 @@ def test_meta_step_matches_oracle(mode, lc):
                 "reward": rew[k, a].T.copy(), "done": dn[k, a].T.astype(bool)}
     agents_o = []
     for a in range(N):
-        agents_o.append(dict(theta=theta0[a], phi=phi0[a], vcrit=vcrit[a][:, None], step=0,
-                             lifetime=int(lv[a, 5]), trajs=[tr_of(k, a) for k in range(K)], eval=tr_of(K, a)))
-    ohyp = ometa.Hypers(lifetime_conditioning=lc)
-    g_ref, aux, _ = ometa.meta_gradient(eta0.cpu().numpy().astype(np.float64), agents_o, ohyp, K)
+        agents_o.append(dict(theta=run["theta0"][a], phi=run["phi0"][a], vcrit=run["vcrit"][a][:, None],
+                             step=int(run["step0"][a]), lifetime=int(lv[a, 5]),
+                             trajs=[tr_of(k, a) for k in range(K)], eval=tr_of(K, a)))
+    with _recorded_clip_norms() as seen:
+        g_ref, aux, _ = ometa.meta_gradient(run["eta0"], agents_o, ohyp, K, dtype=dtype)
+    # meta_gradient walks agent by agent, update by update, actor table (5 columns) then critic table (8)
+    norms = np.array([n for cols, n in seen if cols != 1]).reshape(N, K, 2).transpose(1, 0, 2)
+    return g_ref, aux, norms
+
+
+def _assert_run_matches_oracle(run, g_ref, aux, grad_tol=1e-5):
+    """The file's contract: parameters after K updates rtol/atol 2e-5, metrics 2e-5, meta-gradient relative L2 <
+    grad_tol (1e-5) and cosine > 1 - 1e-9.  Returns (relative L2 error, cosine)."""
+    N = run["theta0"].shape[0]
+    g_gpu, metrics = run["grad"], run["metrics"]
     # parameters after K updates
     for a in range(N):
-        np.testing.assert_allclose(agents.theta[a].cpu().numpy(), aux[a]["theta"], rtol=2e-5, atol=2e-5)
-        np.testing.assert_allclose(agents.phi[a].cpu().numpy(), aux[a]["phi"], rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(run["theta"][a], aux[a]["theta"], rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(run["phi"][a], aux[a]["phi"], rtol=2e-5, atol=2e-5)
     lpg_ref = np.array([x["lpg_loss"] for x in aux])
-    np.testing.assert_allclose(metrics["lpg_loss"].cpu().numpy(), lpg_ref, rtol=2e-5, atol=1e-7)
+    np.testing.assert_allclose(metrics["lpg_loss"], lpg_ref, rtol=2e-5, atol=1e-7)
     for key in ("policy_entropy", "critic_entropy", "policy_l2", "critic_l2", "critic_loss"):
         ref = np.array([x["lpg_agent"][key] for x in aux])
-        np.testing.assert_allclose(metrics["lpg_agent"][key].cpu().numpy(), ref, rtol=2e-5, atol=1e-7, err_msg=key)
+        np.testing.assert_allclose(metrics["lpg_agent"][key], ref, rtol=2e-5, atol=1e-7, err_msg=key)
     err = np.linalg.norm(g_gpu - g_ref) / np.linalg.norm(g_ref)
     cos = float(g_gpu @ g_ref / (np.linalg.norm(g_gpu) * np.linalg.norm(g_ref)))
     print(f"meta-gradient rel L2 {err:.2e}, cosine {cos:.9f}")
-    assert err < 1e-5 and cos > 1 - 1e-9, (err, cos)
+    assert err < grad_tol and cos > 1 - 1e-9, (err, cos)
+    return err, cos
+
+
+@pytest.mark.parametrize("mode,lc", [("dense", False), ("tabular", True), ("mazes", False), ("all_vrandlife", True)])
+def test_meta_step_matches_oracle(mode, lc):
+    N, W, T, K = 3, 64, 20, 3
+    agents, step, eta, adam, hyp, D = _setup(mode, N, W, T, K, lc)
+    run = _run_checked_step(agents, step, eta, adam)
+    g_ref, aux, _ = _oracle_of_run(mode, run, K, T, ometa.Hypers(lifetime_conditioning=lc))
+    _assert_run_matches_oracle(run, g_ref, aux)
 
 
 def test_gru_forward_matches_oracle():
@@ -493,13 +548,38 @@ def test_mini_batches_match_full_batch(nmb):
     assert float((e1 - e2).abs().max()) < 1e-7
 
 
-@pytest.mark.parametrize("mode,N,lc", [("tabular", 512, False), ("all_vrandlife", 16, True)])
-def test_fused_agent_step_matches_dense_path(monkeypatch, mode, N, lc):
+# max_grad_norm of the "clipped" rows below: inside the spread of the 16 agents' gradient norms at these inputs, so
+# one launch holds clipped and unclipped tables (asserted from gstat; at the reference's 0.5 nothing clips here)
+_CLIP_NORM_16 = 0.012
+
+
+def _clip_census(gstat, max_norm):
+    """gstat [..., N, 4] -> the number of (update, agent) entries that were applied with the actor table clipped /
+    unclipped, with the critic table clipped / unclipped, and that were not applied."""
+    g = gstat.detach().cpu().numpy().reshape(-1, 4) if torch.is_tensor(gstat) else np.asarray(gstat).reshape(-1, 4)
+    ap = g[:, 2] > 0.5
+    out = {"actor_clipped": int((ap & (g[:, 0] >= max_norm)).sum()),
+           "actor_unclipped": int((ap & (g[:, 0] < max_norm)).sum()),
+           "critic_clipped": int((ap & (g[:, 1] >= max_norm)).sum()),
+           "critic_unclipped": int((ap & (g[:, 1] < max_norm)).sum()), "not_applied": int((~ap).sum())}
+    q = lambda x: "/".join(f"{v:.2e}" for v in np.quantile(x, (0.0, 0.25, 0.5, 0.75, 1.0)))
+    print(f"max_grad_norm {max_norm}: {out}; quartiles of |G_theta| {q(g[:, 0])}, of |G_phi| {q(g[:, 1])}")
+    return out
+
+
+@pytest.mark.parametrize("mode,N,lc,max_grad_norm", [
+    pytest.param("tabular", 512, False, 0.5, id="tabular-512-False"),
+    pytest.param("all_vrandlife", 16, True, 0.5, id="all_vrandlife-16-True"),
+    pytest.param("all_vrandlife", 16, True, _CLIP_NORM_16, id="all_vrandlife-16-True-clipped")])
+def test_fused_agent_step_matches_dense_path(monkeypatch, mode, N, lc, max_grad_norm):
     """The inner updates as toued_agent_step (theta_{k+1} copied on the side stream, touched rows rewritten,
     gradient rows kept; the reverse pass's entropy gradient and clip-VJP dot fused over those rows) against the
     dense toued_agent_grad + apply + entropy + clip_dot path, over two consecutive meta-steps (the second one's gradient tables hold the first one's rows
     where it does not write): every theta_k / phi_k, the agents, metrics and gstat bit-identical; the
-    meta-gradient up to the clip-VJP dot's summation order (1e-6)."""
+    meta-gradient up to the clip-VJP dot's summation order (1e-6).  At max_grad_norm 0.5 no table clips at these
+    inputs, the dot is multiplied by a zero coefficient and the two gradients are bit-identical; the "clipped" row
+    lowers max_grad_norm into the 16 agents' norms (clipped and unclipped tables in every launch, asserted from
+    gstat), where the dot -- which must skip the stale rows of the previous step -- is live: measured 5e-8."""
     from toued.lpg import init_lpg_params
     from toued.meta import AdamState, LpgHyperparams, MetaGradStep
     W, T, K = 64, 20, 5
@@ -509,7 +589,7 @@ def test_fused_agent_step_matches_dense_path(monkeypatch, mode, N, lc):
     for fused in ("0", "1"):
         monkeypatch.setenv("TOUED_META_FUSED_STEP", fused)
         ag = _clone_agents(ag0)
-        step = MetaGradStep(ro, N, LpgHyperparams(num_agent_updates=K), lc)
+        step = MetaGradStep(ro, N, LpgHyperparams(num_agent_updates=K, max_grad_norm=max_grad_norm), lc)
         assert step.fused_step == (fused == "1")
         hist = []
         for i in range(2):   # the same eta both times (Adam's step would carry the gradients' last-bit difference)
@@ -525,6 +605,10 @@ def test_fused_agent_step_matches_dense_path(monkeypatch, mode, N, lc):
     for (th0, ph0, gs0, g0, m0), (th1, ph1, gs1, g1, m1) in zip(h0, h1):
         assert torch.equal(th0, th1) and torch.equal(ph0, ph1)
         assert torch.equal(gs0, gs1)
+        census = _clip_census(gs0, max_grad_norm)
+        if max_grad_norm != 0.5:   # the clipped row: both branches of both tables in every launch's worth of agents
+            assert min(census[c] for c in ("actor_clipped", "actor_unclipped", "critic_clipped",
+                                           "critic_unclipped")) > 0, census
         for k in m0["lpg_agent"]:
             assert torch.equal(m0["lpg_agent"][k], m1["lpg_agent"][k]), k
         for k in ("lpg_loss", "lpg_agent_return"):
@@ -534,12 +618,17 @@ def test_fused_agent_step_matches_dense_path(monkeypatch, mode, N, lc):
         assert rel < 1e-6
 
 
-@pytest.mark.parametrize("mode,N,lc", [("tabular", 512, False), ("all_vrandlife", 16, True)])
-def test_one_launch_update_and_reverse_step_bit_identical(monkeypatch, mode, N, lc):
+@pytest.mark.parametrize("mode,N,lc,max_grad_norm", [
+    pytest.param("tabular", 512, False, 0.5, id="tabular-512-False"),
+    pytest.param("all_vrandlife", 16, True, 0.5, id="all_vrandlife-16-True"),
+    pytest.param("all_vrandlife", 16, True, _CLIP_NORM_16, id="all_vrandlife-16-True-clipped")])
+def test_one_launch_update_and_reverse_step_bit_identical(monkeypatch, mode, N, lc, max_grad_norm):
     """toued_agent_step_entropy (the inner update and its entropy metrics in one launch) and toued_entropy_clip_hvp
     (the reverse pass's entropy-clip and HVP of step k in one launch, one sort) against the separate launches
     (TOUED_STEP_ENTROPY=0, TOUED_REVERSE_PAIR=0), over two consecutive meta-steps: the meta-gradient, every
-    theta_k / phi_k, the adjoint's cotangents d_pi_hat / d_y_hat, the agents and the metrics bit-identical."""
+    theta_k / phi_k, the adjoint's cotangents d_pi_hat / d_y_hat, gstat, the agents and the metrics bit-identical.
+    The "clipped" row lowers max_grad_norm into the agents' gradient norms: clipped, unclipped and not-applied
+    updates in one step (asserted from gstat)."""
     from toued.lpg import init_lpg_params
     from toued.meta import AdamState, LpgHyperparams, MetaGradStep
     from toued.env import L_LIFETIME
@@ -555,7 +644,7 @@ def test_one_launch_update_and_reverse_step_bit_identical(monkeypatch, mode, N, 
         monkeypatch.setenv("TOUED_STEP_ENTROPY", one)
         monkeypatch.setenv("TOUED_REVERSE_PAIR", one)
         ag = _clone_agents(ag0)
-        step = MetaGradStep(ro, N, LpgHyperparams(num_agent_updates=K), lc)
+        step = MetaGradStep(ro, N, LpgHyperparams(num_agent_updates=K, max_grad_norm=max_grad_norm), lc)
         assert step.fused_step and step.step_entropy == (one == "1") and step.reverse_pair == (one == "1")
         hist = []
         for i in range(2):
@@ -564,15 +653,19 @@ def test_one_launch_update_and_reverse_step_bit_identical(monkeypatch, mode, N, 
                        AdamState(eta.numel(), "cuda"), ag)
             torch.cuda.synchronize()
             hist.append((step.theta_h.clone(), step.phi_h.clone(), step.d_pi_hat.clone(), step.d_y_hat.clone(),
-                         step.grad.clone(), met))
+                         step.grad.clone(), step.gstat.clone(), met))
         out.append((ag, hist))
     (a0, h0), (a1, h1) = out
     for name in ("theta", "phi", "step", "state", "vstep"):
         assert torch.equal(getattr(a0, name), getattr(a1, name)), name
     for x0, x1 in zip(h0, h1):
-        for j in range(5):
+        for j in range(6):
             assert torch.equal(x0[j], x1[j]), j
-        m0, m1 = x0[5], x1[5]
+        census = _clip_census(x0[5], max_grad_norm)
+        if max_grad_norm != 0.5:   # the clipped row: clipped, unclipped and not-applied updates in one step
+            assert min(census[c] for c in ("actor_clipped", "actor_unclipped", "critic_clipped", "critic_unclipped",
+                                           "not_applied")) > 0, census
+        m0, m1 = x0[6], x1[6]
         for k in m0["lpg_agent"]:
             assert torch.equal(m0["lpg_agent"][k], m1["lpg_agent"][k]), k
         for k in ("lpg_loss", "reg_lpg_loss", "lpg_agent_return"):
@@ -625,38 +718,57 @@ def test_1024_agents_two_mini_batches_on_one_gpu():
     assert float((g_sum - g_big).norm() / g_big.norm()) < 1e-6
 
 
+# (max_grad_norm, value-critic updates clipped of the N * (K + 1)) of test_fix_value_critic_matches_oracle: the
+# reference's 0.5, and a second value on the other side of the value-critic gradient norms at these inputs
+_VCRIT_CLIP_CASES = ((0.5, 0), (0.05, 12))
+
+
 def test_fix_value_critic_matches_oracle():
     """--fix_value_critic (SURVEY B.3 fixed): the value critic takes K SGD updates on the train rollouts, the
     eval advantages / value loss use those parameters, then one update on the eval rollout — vs the float64
-    oracle (oracle/meta.value_critic_step); the meta-gradient and agent tables as in the frozen case."""
+    oracle (oracle/meta.value_critic_step); the meta-gradient and agent tables as in the frozen case.  Run at two
+    max_grad_norm values so that the value-critic update's clipped and unclipped branches (a reciprocal clip scale
+    on the device) both occur: which one each of the N * (K + 1) updates takes is read from the oracle's float64
+    gradient norms, every norm at least 2 % away from max_grad_norm."""
     N, W, T, K = 3, 64, 20, 3
-    agents, step, eta, adam, hyp, D = _setup("dense", N, W, T, K)
-    step.hyp.fix_value_critic = True
-    th0, ph0, vc0 = agents.theta.cpu().numpy(), agents.phi.cpu().numpy(), agents.vcrit.cpu().numpy()
-    lv = agents.levels.cpu().numpy()
-    eta0 = eta.cpu().numpy().astype(np.float64)
-    metrics = step(torch.tensor([0, 41], dtype=torch.int32, device="cuda"), eta, adam, agents)
-    torch.cuda.synchronize()
-    tr = step.traj
-    idx, tm, act = tr.obs_idx.cpu().numpy(), tr.obs_time.cpu().numpy(), tr.action.cpu().numpy()
-    rew, dn = tr.reward.cpu().numpy(), tr.done.cpu().numpy()
+    branches = set()
+    for max_norm, n_clipped in _VCRIT_CLIP_CASES:
+        agents, step, eta, adam, hyp, D = _setup("dense", N, W, T, K, max_grad_norm=max_norm)
+        step.hyp.fix_value_critic = True
+        th0, ph0, vc0 = agents.theta.cpu().numpy(), agents.phi.cpu().numpy(), agents.vcrit.cpu().numpy()
+        lv = agents.levels.cpu().numpy()
+        eta0 = eta.cpu().numpy().astype(np.float64)
+        metrics = step(torch.tensor([0, 41], dtype=torch.int32, device="cuda"), eta, adam, agents)
+        torch.cuda.synchronize()
+        tr = step.traj
+        idx, tm, act = tr.obs_idx.cpu().numpy(), tr.obs_time.cpu().numpy(), tr.action.cpu().numpy()
+        rew, dn = tr.reward.cpu().numpy(), tr.done.cpu().numpy()
 
-    def tr_of(k, a):
-        return {"idx": idx[k, a].T.copy(), "time": tm[k, a].T.copy(), "action": act[k, a].T.astype(np.int64),
-                "reward": rew[k, a].T.copy(), "done": dn[k, a].T.astype(bool)}
-    ags = [dict(theta=th0[a], phi=ph0[a], vcrit=vc0[a][:, None], step=0, lifetime=int(lv[a, 5]),
-                trajs=[tr_of(k, a) for k in range(K)], eval=tr_of(K, a)) for a in range(N)]
-    g_ref, aux, _ = ometa.meta_gradient(eta0, ags, ometa.Hypers(fix_value_critic=True), K)
-    vc = agents.vcrit.cpu().numpy().astype(np.float64)
-    for a in range(N):
-        dv, dv_ref = vc[a] - vc0[a], aux[a]["vcrit"][:, 0] - vc0[a]
-        assert np.linalg.norm(dv - dv_ref) <= 2e-5 * np.linalg.norm(dv_ref) + 1e-9, a
-    assert agents.vstep.cpu().tolist() == [K + 1] * N
-    np.testing.assert_allclose(metrics["value_loss"].cpu().numpy(), [x["value_loss"] for x in aux], rtol=2e-5)
-    np.testing.assert_allclose(metrics["lpg_loss"].cpu().numpy(), [x["lpg_loss"] for x in aux], rtol=2e-5,
-                               atol=1e-7)
-    g = step.grad.cpu().numpy() / N
-    assert np.linalg.norm(g - g_ref) / np.linalg.norm(g_ref) < 1e-5
+        def tr_of(k, a):
+            return {"idx": idx[k, a].T.copy(), "time": tm[k, a].T.copy(), "action": act[k, a].T.astype(np.int64),
+                    "reward": rew[k, a].T.copy(), "done": dn[k, a].T.astype(bool)}
+        ags = [dict(theta=th0[a], phi=ph0[a], vcrit=vc0[a][:, None], step=0, lifetime=int(lv[a, 5]),
+                    trajs=[tr_of(k, a) for k in range(K)], eval=tr_of(K, a)) for a in range(N)]
+        with _recorded_clip_norms() as seen:
+            g_ref, aux, _ = ometa.meta_gradient(eta0, ags, ometa.Hypers(fix_value_critic=True, max_grad_norm=max_norm),
+                                                K)
+        vnorm = np.array([n for cols, n in seen if cols == 1])
+        assert vnorm.size == N * (K + 1)
+        print(f"max_grad_norm {max_norm}: value-critic gradient norms {np.array2string(vnorm, precision=4)}")
+        assert np.all(np.abs(vnorm / max_norm - 1.0) >= 0.02), vnorm
+        assert int((vnorm >= max_norm).sum()) == n_clipped, vnorm
+        branches |= set((vnorm >= max_norm).tolist())
+        vc = agents.vcrit.cpu().numpy().astype(np.float64)
+        for a in range(N):
+            dv, dv_ref = vc[a] - vc0[a], aux[a]["vcrit"][:, 0] - vc0[a]
+            assert np.linalg.norm(dv - dv_ref) <= 2e-5 * np.linalg.norm(dv_ref) + 1e-9, a
+        assert agents.vstep.cpu().tolist() == [K + 1] * N
+        np.testing.assert_allclose(metrics["value_loss"].cpu().numpy(), [x["value_loss"] for x in aux], rtol=2e-5)
+        np.testing.assert_allclose(metrics["lpg_loss"].cpu().numpy(), [x["lpg_loss"] for x in aux], rtol=2e-5,
+                                   atol=1e-7)
+        g = step.grad.cpu().numpy() / N
+        assert np.linalg.norm(g - g_ref) / np.linalg.norm(g_ref) < 1e-5
+    assert branches == {True, False}, branches
 
 
 @pytest.mark.parametrize("F,per_agent", [(5, False), (7, True)])

@@ -73,46 +73,74 @@ def _a2c_setup(mode, N, W, T, seed=0, scale=20.0):
     return ro, levels, p, lt, theta, vcrit, state, D
 
 
+# max_grad_norm values of test_a2c_update_matches_oracle: the reference's 0.5, and a second one on the other side of
+# the gradient norms at these inputs, so both tables take both branches (clipped / unclipped) of the device's
+# reciprocal clip scale
+_A2C_MAX_NORMS = (0.5, 0.005)
+
+
 @pytest.mark.parametrize("fused", [True, False])
 def test_a2c_update_matches_oracle(fused):
-    """fused: the LDS-table update kernel (toued_a2c_update); else toued_a2c_grad + toued_a2c_apply."""
+    """fused: the LDS-table update kernel (toued_a2c_update); else toued_a2c_grad + toued_a2c_apply.  Which clip branch
+    each agent's actor and critic update takes is read from the oracle's float64 gradient norms (each at least 2 %
+    away from max_norm); over the max_norm values both tables take both branches."""
     from toued.a2c import A2CHyperparams, A2CTrainer
     mode, N, W, T = "dense", 3, 64, 20
-    ro, levels, p, lt, theta, vcrit, state, D = _a2c_setup(mode, N, W, T)
     spec = olv.env_spec(mode)
-    th0, vc0, st0 = theta.cpu().numpy(), vcrit.cpu().numpy(), state.cpu().numpy()
-    rng = jr.split(jr.PRNGKey(9), N)
-    # one launch per update (the chain kernel keeps its trajectories in LDS; its parity with this path:
-    # test_a2c_chain_matches_launch_per_update)
-    tr = A2CTrainer(ro, A2CHyperparams(), _ahyp(mode), use_graph=False, fused=fused, chain=False)
-    step = torch.zeros(N, dtype=torch.int32, device="cuda")
-    loss = tr.train(dk(rng), theta, vcrit, step, levels, state, 1).cpu().numpy()
-    b = tr._bufs["tr"]
-    idx, tm, act = b.obs_idx.cpu().numpy(), b.obs_time.cpu().numpy(), b.action.cpu().numpy()
-    rew, dn = b.reward.cpu().numpy(), b.done.cpu().numpy()
-    # rollout of update 0 with key split(rng)[1], bit-exact
-    sub = jr.split(rng, 2)[:, 1]
-    otr, _, _ = oro.batch_rollout(spec, sub, th0, p, _ost(st0, spec.max_n_objs), T)
-    assert np.array_equal(act, otr["action"].transpose(0, 2, 1))
-    assert np.array_equal(idx, otr["idx"].transpose(0, 2, 1))
-    assert np.array_equal(rew, otr["reward"].transpose(0, 2, 1))
-    assert step.cpu().numpy().tolist() == [1] * N
-    th1, vc1 = theta.cpu().numpy(), vcrit.cpu().numpy()
-    hyp = ometa.Hypers()
-    for a in range(N):
-        traj = {"idx": idx[a].T.copy(), "time": tm[a].T.copy(), "action": act[a].T.astype(np.int64),
-                "reward": rew[a].T.copy(), "done": dn[a].T.astype(bool)}
-        t_ref, v_ref, s_ref, al, cl = oa2c.a2c_step(
-            torch.from_numpy(th0[a].astype(np.float64)), torch.from_numpy(vc0[a][:, None].astype(np.float64)), 0,
-            int(lt[a]), traj, hyp, 40.0, 4.0, 0.5)
-        dt_ref = t_ref.numpy() - th0[a]
-        dv_ref = v_ref.numpy()[:, 0] - vc0[a]
-        dt = th1[a].astype(np.float64) - th0[a]
-        dv = vc1[a].astype(np.float64) - vc0[a]
-        assert np.linalg.norm(dt - dt_ref) <= 1e-4 * np.linalg.norm(dt_ref) + 1e-6, a
-        assert np.linalg.norm(dv - dv_ref) <= 1e-4 * np.linalg.norm(dv_ref) + 1e-6, a
-        assert abs(loss[a, 0] - al) <= 1e-4 * max(1.0, abs(al))
-        assert abs(loss[a, 1] - cl) <= 1e-4 * max(1.0, abs(cl))
+    branches = set()
+    for max_norm in _A2C_MAX_NORMS:
+        ro, levels, p, lt, theta, vcrit, state, D = _a2c_setup(mode, N, W, T)
+        th0, vc0, st0 = theta.cpu().numpy(), vcrit.cpu().numpy(), state.cpu().numpy()
+        rng = jr.split(jr.PRNGKey(9), N)
+        # one launch per update (the chain kernel keeps its trajectories in LDS; its parity with this path:
+        # test_a2c_chain_matches_launch_per_update)
+        ah = _ahyp(mode)
+        ah.max_grad_norm = max_norm
+        tr = A2CTrainer(ro, A2CHyperparams(), ah, use_graph=False, fused=fused, chain=False)
+        step = torch.zeros(N, dtype=torch.int32, device="cuda")
+        loss = tr.train(dk(rng), theta, vcrit, step, levels, state, 1).cpu().numpy()
+        b = tr._bufs["tr"]
+        idx, tm, act = b.obs_idx.cpu().numpy(), b.obs_time.cpu().numpy(), b.action.cpu().numpy()
+        rew, dn = b.reward.cpu().numpy(), b.done.cpu().numpy()
+        # rollout of update 0 with key split(rng)[1], bit-exact
+        sub = jr.split(rng, 2)[:, 1]
+        otr, _, _ = oro.batch_rollout(spec, sub, th0, p, _ost(st0, spec.max_n_objs), T)
+        assert np.array_equal(act, otr["action"].transpose(0, 2, 1))
+        assert np.array_equal(idx, otr["idx"].transpose(0, 2, 1))
+        assert np.array_equal(rew, otr["reward"].transpose(0, 2, 1))
+        assert step.cpu().numpy().tolist() == [1] * N
+        th1, vc1 = theta.cpu().numpy(), vcrit.cpu().numpy()
+        hyp = ometa.Hypers()
+        norms = []
+        clip_sgd = oa2c.clip_sgd
+
+        def recording_clip_sgd(params, grad, lr, mn):
+            norms.append(float(torch.sqrt(torch.sum(grad.double() ** 2))))
+            return clip_sgd(params, grad, lr, mn)
+        for a in range(N):
+            traj = {"idx": idx[a].T.copy(), "time": tm[a].T.copy(), "action": act[a].T.astype(np.int64),
+                    "reward": rew[a].T.copy(), "done": dn[a].T.astype(bool)}
+            oa2c.clip_sgd = recording_clip_sgd
+            try:
+                t_ref, v_ref, s_ref, al, cl = oa2c.a2c_step(
+                    torch.from_numpy(th0[a].astype(np.float64)), torch.from_numpy(vc0[a][:, None].astype(np.float64)),
+                    0, int(lt[a]), traj, hyp, 40.0, 4.0, max_norm)
+            finally:
+                oa2c.clip_sgd = clip_sgd
+            dt_ref = t_ref.numpy() - th0[a]
+            dv_ref = v_ref.numpy()[:, 0] - vc0[a]
+            dt = th1[a].astype(np.float64) - th0[a]
+            dv = vc1[a].astype(np.float64) - vc0[a]
+            assert np.linalg.norm(dt - dt_ref) <= 1e-4 * np.linalg.norm(dt_ref) + 1e-6, a
+            assert np.linalg.norm(dv - dv_ref) <= 1e-4 * np.linalg.norm(dv_ref) + 1e-6, a
+            assert abs(loss[a, 0] - al) <= 1e-4 * max(1.0, abs(al))
+            assert abs(loss[a, 1] - cl) <= 1e-4 * max(1.0, abs(cl))
+        norms = np.array(norms).reshape(N, 2)    # per agent: actor, critic (oracle/a2c.py: the order of its two clips)
+        print(f"max_norm {max_norm}: |g_actor| {norms[:, 0]}, |g_critic| {norms[:, 1]}")
+        assert np.all(np.abs(norms / max_norm - 1.0) >= 0.02), norms
+        for t, name in enumerate(("actor", "critic")):
+            branches |= {(name, bool(c)) for c in norms[:, t] >= max_norm}
+    assert branches == {("actor", True), ("actor", False), ("critic", True), ("critic", False)}, branches
 
 
 def test_a2c_graph_replay_matches_eager_and_lifetime_discard():
