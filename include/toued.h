@@ -330,6 +330,16 @@ int toued_adam(int P, float* eta, const float* grad, float* m, float* v, float n
  * scan fused on their staged trajectories (k_eval_loss, k_a2c_update). */
 int toued_gae(int N, int W, int T, const float* value, const float* reward, const uint8_t* done, float gamma,
               float gamma_lambda, float* adv, float* target, hipStream_t stream);
+/* Value-loss PLR scores of N agents' trajectories in toued_rollout's layout (tidx / ttime [N][T+1][W], trew / tdone
+ * [N][T][W]) under their value critics vcrit [N][D]: v = vcrit[a][idx] + ((float)time * 0.001f) * vcrit[a][D-1] (the
+ * critic of toued_eval_loss), then toued_gae's scan on it, fused: pvl[a] = mean over the W * T (worker, step) pairs
+ * of max(gae, 0) (positive value loss), l1[a] = mean of |gae| (L1 value loss).  Either of pvl / l1 may be null (not
+ * both); adv (nullable, [N][T][W]) receives the advantages, bit-exact with toued_gae on the gathered values.  The
+ * sums are kept in f64 in a fixed order and rounded to f32 once: deterministic, and agent a's scores depend on agent
+ * a's rows only.  Any W, T >= 1; 2 <= D <= 8192; W * T < 2^31. */
+int toued_value_loss_scores(int N, int W, int T, int D, const float* vcrit, const int* tidx, const int* ttime,
+                            const float* trew, const uint8_t* tdone, float gamma, float gamma_lambda, float* pvl,
+                            float* l1, float* adv, hipStream_t stream);
 
 /* ---- LPG reverse-time GRU on MFMA (models/lpg.py:11-35, flax GRUCell) ---- */
 size_t toued_gru_packed_floats(int which);

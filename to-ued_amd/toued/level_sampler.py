@@ -4,8 +4,11 @@
 ``initial_sample``, ``sample``, ``rollout_manager``, ``max_lifetime``.
 Score functions: ``random`` (domain randomisation), ``frozen`` (uniform replay
 of a fixed buffer), ``alg_regret`` (PLR with the A2C antagonist's
-algorithmic regret, GROOVE) and ``optimal_regret`` (PLR with the true regret
-against the level's exact optimal return; tabular modes, not in the reference).
+algorithmic regret, GROOVE), ``positive_value_loss`` / ``l1_value_loss`` (PLR
+with the mean of max(GAE, 0) / |GAE| of the agent's eval trajectory under its
+value critic; not with --use_es, not in the reference) and ``optimal_regret``
+(PLR with the true regret against the level's exact optimal return; tabular
+modes, not in the reference).
 All state is device-resident; per-agent work is
 computed for the whole batch and masked by ``terminated`` exactly like the
 reference's vmapped ``jnp.where`` (the masked-out work has no observable effect).
@@ -24,7 +27,8 @@ from .agents import (DENSE0_HASH, AgentBatch, AgentHyperparams, create_agents, c
 from .env import L_BUFID, L_LIFETIME, LevelGenerator, get_env_spec
 from .rollout import RolloutWrapper
 
-SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "optimal_regret"]
+SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
+VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
 SCORE_TRANSFORMS = ["proportional", "rank"]
 
 
@@ -70,6 +74,9 @@ class LevelSampler:
         if args.score_function == "optimal_regret" and not self.spec.tabular:
             raise ValueError(f"Level score function optimal_regret needs a tabular environment mode: the optimal "
                              f"return is not defined for {self.env_mode}")
+        if args.score_function in VALUE_LOSS_FUNCTIONS and args.use_es:
+            raise ValueError(f"Level score function {args.score_function} needs the agents' value critics, which "
+                             f"--use_es does not train")
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
         if args.score_function not in SCORE_FUNCTIONS:

@@ -9,6 +9,10 @@
   4. toued_plr_sample: replay ids (rank or proportional), random new ids, the bernoulli/permutation
      selection (:203-227); ``active[new_ids] = True`` (:232-234).
 
+With ``score_function = positive_value_loss`` or ``l1_value_loss`` (not in the reference) step 2 is
+``value_loss_scores``: one eval rollout of the LPG agent and the mean of max(GAE, 0) or |GAE| under the agent's own
+value critic (toued_value_loss_scores), no antagonist; the rest is unchanged.
+
 With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
 exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
 
@@ -31,6 +35,7 @@ from .a2c import A2CHyperparams, A2CTrainer
 from .debug import nan_checker
 from .agents import AgentBatch, create_agents, eval_agent, eval_agent_reset
 from .env import L_BUFID
+from .rollout import Transition
 
 
 def _split2(rng):
@@ -115,6 +120,65 @@ def optimal_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta:
 REGRET_FUNCTIONS = {"alg_regret": algorithmic_regret, "optimal_regret": optimal_regret}
 
 
+# value_loss_scores keeps one chunk of agents' eval trajectories at a time (14 bytes per worker and step) under this
+VALUE_LOSS_SCRATCH_BYTES = 1 << 30
+
+
+def value_loss_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
+                      vcrit: torch.Tensor, chunk_agents: int | None = None):
+    """The value-loss PLR scores of n LPG agents: (positive value loss, L1 value loss), f32 [n] each, the means over
+    the agent's eval trajectory (``env_workers`` workers, ``eval_rollout_len`` steps) of max(GAE, 0) and |GAE| under
+    its value critic ``vcrit`` [n, obs_dim] (AgentBatch.vcrit, the critic of meta/train.py:61-100), with the
+    sampler's --gamma and --gae_lambda.  No antagonist and no optimal return: one eval rollout and one kernel
+    (RolloutWrapper.value_loss_scores).  The LPG agent's key is ``algorithmic_regret``'s ``lpg_rng`` (the splits of
+    level_sampler.py:293-329) and the worker reset and rollout key are ``eval_agent``'s, so the scored trajectory
+    is the one whose return the regret scores use.  An extension: the reference's LevelSampler has no such score.
+
+    The agents go through in chunks whose trajectories fit VALUE_LOSS_SCRATCH_BYTES (``chunk_agents`` overrides the
+    chunk size); an agent's scores depend on its own key, level, actor and critic only, so the chunking changes
+    no bit."""
+    n = keys.shape[0]
+    dev = keys.device
+    pvl = torch.empty(n, dtype=torch.float32, device=dev)
+    l1 = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return pvl, l1
+    ro = sampler.rollout_manager
+    W = sampler.env_workers
+    vcrit = vcrit.reshape(n, ro.obs_dim)
+    rng, _ = _split2(keys)
+    rng, _ = _split2(rng)
+    lpg_rng, _ = _split2(rng)
+    if chunk_agents is None:
+        chunk_agents = VALUE_LOSS_SCRATCH_BYTES // (14 * W * (ro.eval_rollout_len + 1))
+    chunk_agents = max(1, min(int(chunk_agents), n))
+    out = None
+    for lo in range(0, n, chunk_agents):
+        hi = min(lo + chunk_agents, n)
+        lv = levels[lo:hi].contiguous()
+        state, ro_keys = eval_agent_reset(ro, lpg_rng[lo:hi].contiguous(), lv, W)
+        if out is not None and hi - lo < chunk_agents:       # the last, shorter chunk: the buffers' leading rows
+            out = Transition(*(getattr(out, f)[:hi - lo] for f in ("obs_idx", "obs_time", "action", "reward", "done")))
+        out, _, _ = ro.batch_rollout(ro_keys, lpg_theta[lo:hi].contiguous(), lv, state, eval=True, out=out,
+                                     inplace_state=True)
+        p, l = ro.value_loss_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, sampler.args.gae_lambda)
+        pvl[lo:hi] = p
+        l1[lo:hi] = l
+    return pvl, l1
+
+
+def positive_value_loss(sampler, keys, levels, lpg_theta, vcrit) -> torch.Tensor:
+    return value_loss_scores(sampler, keys, levels, lpg_theta, vcrit)[0]
+
+
+def l1_value_loss(sampler, keys, levels, lpg_theta, vcrit) -> torch.Tensor:
+    return value_loss_scores(sampler, keys, levels, lpg_theta, vcrit)[1]
+
+
+# the scores that read the agents' value critics: the regret functions' arguments plus AgentBatch.vcrit's rows
+VALUE_LOSS_FUNCTIONS = {"positive_value_loss": positive_value_loss, "l1_value_loss": l1_value_loss}
+
+
 # the regret round's eval draws ([eval_len][2n * W][4] u32, plus as much key-chain scratch) are made ahead when they fit
 EVAL_DRAWS_MAX_BYTES = 4 << 30
 
@@ -138,6 +202,10 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     """Returns (rng, buffer, new_levels [n_local, 64]) — new_levels for terminated agents, the
     caller keeps the old level elsewhere (``term_mask_fn``)."""
     world = sampler.world
+    value_loss = VALUE_LOSS_FUNCTIONS.get(sampler.score_function)
+    if value_loss is not None and agents.vcrit is None:
+        raise ValueError(f"Level score function {sampler.score_function} needs the agents' value critics "
+                         f"(AgentBatch.vcrit is None)")
     N = agents.n if sl is None else sl[2]
     B = len(buffer)
     dev = agents.levels.device
@@ -160,14 +228,19 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     if sl is not None:
         keys = keys[sl[0]:sl[1]].contiguous()
     score = torch.zeros(agents.n, dtype=torch.float32, device=dev)
-    regret = REGRET_FUNCTIONS[sampler.score_function]
+    if value_loss is not None:
+        vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
+        regret = lambda s, k, lv, th, sel=slice(None): value_loss(s, k, lv, th, vcrit[sel].contiguous())
+    else:
+        score_fn = REGRET_FUNCTIONS[sampler.score_function]
+        regret = lambda s, k, lv, th, sel=None: score_fn(s, k, lv, th)
     if sampler.regret_all_agents:
         score = regret(sampler, keys, agents.levels, agents.theta)
     else:
         sel = term.nonzero().flatten()
         if sel.numel():
             score[sel] = regret(sampler, keys[sel].contiguous(), agents.levels[sel].contiguous(),
-                                agents.theta[sel].contiguous())
+                                agents.theta[sel].contiguous(), sel)
     nan_checker().check("regret_scores", score)
     old_ids = agents.levels[:, L_BUFID].contiguous()
     if world is not None and world.active:

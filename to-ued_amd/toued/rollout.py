@@ -16,6 +16,7 @@ import os
 
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -211,6 +212,30 @@ class RolloutWrapper:
         _lib.call("toued_optimal_return", _lib.ptr(levels), n, self.spec.max_grid_size, self.spec.max_n_objs,
                   int(self.spec.tabular), L, _lib.ptr(v0), _lib.ptr(v_all), _lib.stream_ptr())
         return v_all if return_all else v0
+
+    def value_loss_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float, gae_lambda: float,
+                          return_adv: bool = False):
+        """The value-loss PLR scores of N agents' trajectories under their value critics ``vcrit`` f32 [N, D]
+        (toued_value_loss_scores: value gather, GAE and both means in one launch, no host synchronisation):
+        (positive value loss, L1 value loss), f32 [N] each, the means over workers and steps of max(GAE, 0) and |GAE|
+        with the value of meta/train.py:61-100 and the scan of util/metrics.py:17-38.  ``return_adv``: also the
+        advantages f32 [N, T, W], bit-identical to toued.metrics.gae on the gathered values."""
+        N, T, W = transition.reward.shape
+        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
+                or transition.done.shape != (N, T, W):
+            raise ValueError(f"value_loss_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
+                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
+        vcrit = vcrit.reshape(N, vcrit.shape[1]).contiguous()     # [N, D] or the critic table [N, D, 1]
+        dev = transition.reward.device
+        pvl = torch.empty(N, dtype=torch.float32, device=dev)
+        l1 = torch.empty(N, dtype=torch.float32, device=dev)
+        adv = torch.empty((N, T, W), dtype=torch.float32, device=dev) if return_adv else None
+        # discount * gae_lambda is a python-float product in the reference (weak-typed, rounded to f32 once)
+        gl = float(np.float32(float(gamma) * float(gae_lambda)))
+        _lib.call("toued_value_loss_scores", N, W, T, vcrit.shape[1], _lib.ptr(vcrit), _lib.ptr(transition.obs_idx),
+                  _lib.ptr(transition.obs_time), _lib.ptr(transition.reward), _lib.ptr(transition.done), float(gamma),
+                  gl, _lib.ptr(pvl), _lib.ptr(l1), _lib.ptr(adv), _lib.stream_ptr())
+        return (pvl, l1, adv) if return_adv else (pvl, l1)
 
     def eval_returns(self, agent_keys: torch.Tensor, theta: torch.Tensor, levels: torch.Tensor,
                      state: torch.Tensor) -> torch.Tensor:
