@@ -165,6 +165,17 @@ int toued_eval_returns_cus(int n_workers);
  * n == 0 and max_rollout_len == 0 succeed (v0 = 0). */
 int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int tabular, int max_rollout_len,
                          float* v0, float* v_all, hipStream_t stream);
+/* The exact expected return of n tabular agents' own policies on their levels (RolloutWrapper.policy_return): the
+ * recursion of toued_optimal_return with v_t(s) = sum_a pi_t(a|s) q_t(s, a) in place of the max, where pi_t(.|s) is
+ * the softmax of the f32 logits theta[s][a] + fl(fl(t * 0.001f) * theta[D-1][a]) (the rollout kernels' actor),
+ * evaluated in f64.  levels [n][LEVEL_WORDS], theta [n][D][5] with D = max_grid^2 * 2^n_max + 1 (row D-1: the
+ * time-feature weights); v0 [n] and v_all (nullable) [n][max_rollout_len][S] as toued_optimal_return's.  v0 is the
+ * expectation of the first-episode return that an eval rollout of max_rollout_len steps samples.  One launch, no
+ * atomics, run-to-run bit-identical; level i's result depends on levels[i] and theta[i] only.  -1 for tabular == 0
+ * (unsupported), D != S + 1, negative n or max_rollout_len, max_grid outside [1, 16], n_max outside
+ * [0, TOUED_MAX_OBJS] or a table over the LDS budget; n == 0 and max_rollout_len == 0 succeed (v0 = 0). */
+int toued_policy_return(const int* levels, const float* theta, int n, int D, int max_grid, int n_max, int tabular,
+                        int max_rollout_len, float* v0, float* v_all, hipStream_t stream);
 
 
 /* ---- Level sampler (environments/level_sampler.py) ---- */

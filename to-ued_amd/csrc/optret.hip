@@ -24,6 +24,9 @@
 //   * One LDS-only barrier per time step; the only global traffic inside the loop is the optional v_all row store.
 //   * Only the count of unmasked steps matters (v_t is zero for t >= max_steps_in_episode): H = min(max_steps,
 //     max_rollout_len) backups give v_0, and the rows t >= max_steps of v_all are zero fills.
+//
+// k_policy_return (further down) is the same recursion for the expected return of a tabular agent's own policy,
+// v_t(s) = sum_a pi_t(a|s) q(s, a), on the same setup (optret_setup).
 #include "env_dev.h"
 
 namespace {
@@ -39,9 +42,19 @@ __host__ __device__ inline size_t optret_lds_bytes(int G2, int n_max) {
   return (b + 15) & ~(size_t)15;
 }
 
-__global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, int n_max, int L,
-                                 float* __restrict__ v0, float* __restrict__ v_all) {
-  extern __shared__ __align__(16) unsigned char smem[];
+// The per-level tables of both kernels, in dynamic LDS, and the level's scalars.
+struct OptretSetup {
+  double *va, *pw, *rsum, *keepw;
+  const int* lev;
+  const uint16_t* nxt;
+  const uint8_t *cells, *eord;
+  int G2, S, NE, used, ne, H, ncell;
+};
+
+// Builds the tables of level blockIdx.x (see the head of this file), fills both value tables with v_H and the rows
+// t >= max_steps of v_all with zeros, and ends with a block barrier.
+__device__ __forceinline__ OptretSetup optret_setup(unsigned char* smem, const int* __restrict__ levels, int max_grid,
+                                                    int n_max, int L, float* __restrict__ v_all) {
   const int G2 = max_grid * max_grid;
   const int S = G2 << n_max;
   const int NE = 1 << n_max;
@@ -140,7 +153,23 @@ __global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, i
   }
   __syncthreads();
 
-  const int ncell = s_ncell;
+  return OptretSetup{va, pw, rsum, keepw, lev, nxt, cells, eord, G2, S, NE, used, ne, H, s_ncell};
+}
+
+__global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, int n_max, int L,
+                                 float* __restrict__ v0, float* __restrict__ v_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+  double* const va = T.va;
+  const double *pw = T.pw, *rsum = T.rsum, *keepw = T.keepw;
+  const int* lev = T.lev;
+  const uint16_t* nxt = T.nxt;
+  const uint8_t *cells = T.cells, *eord = T.eord;
+  const int G2 = T.G2, S = T.S, NE = T.NE, used = T.used, ne = T.ne, H = T.H;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const float ninf = -__builtin_inff();
+
+  const int ncell = T.ncell;
   const int nwork = ncell * ne;
   int curo = 0;    // v_t, written: table va (offset 0) or vb (offset S) of the 2S-entry array
   int nxo = S;     // v_{t+1}, read
@@ -197,6 +226,149 @@ __global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, i
   if (tid == 0) v0[blockIdx.x] = H > 0 ? (float)va[nxo + lev[L_START] + G2 * used] : 0.0f;
 }
 
+// One policy backup: v_t(pos, e) = sum_a pi(a) q(s, a) into table `curo`, with the policy's f32 logits l[5] (as
+// actor_probs5 forms them) and k_optimal_return's outcome loop on table `nxo`.  The softmax is exp(l - max) / sum in
+// f64; the argmax term is exp(0) = 1, so the sum is >= 1: huge logits give an exact one-hot policy and no NaN.
+__device__ __forceinline__ void policy_backup(const OptretSetup& T, int nxo, int curo, int pos, int e,
+                                              const float* l) {
+  double* const va = T.va;
+  const double* pw = T.pw;
+  const int G2 = T.G2, NE = T.NE;
+  const int absent = T.used & ~e;
+  const double* pwa = pw + absent * NE;
+  int base[5], col[5];
+  double ev[5];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const uint32_t en = T.nxt[pos * 5 + a];
+    col[a] = (int)(en >> 8) & e;
+    base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~col[a]);
+    ev[a] = 0.0;
+  }
+  int R0 = 0;
+  do {
+    const int R1 = (R0 - absent) & absent;
+    const double p0 = pwa[R0];
+    const double p1 = pw[R1 != 0 ? absent * NE + R1 : NE * NE];   // pw[NE * NE] = 0
+    const int o0 = G2 * R0, o1 = G2 * R1;
+    double x0[5], x1[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) { x0[a] = va[base[a] + o0]; x1[a] = va[base[a] + o1]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int a = 0; a < 5; ++a) ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
+    R0 = R1 != 0 ? (R1 - absent) & absent : 0;
+  } while (R0 != 0);
+  float m = l[0];
+#pragma unroll
+  for (int a = 1; a < 5; ++a) m = fmaxf(m, l[a]);
+  double num = 0.0, den = 0.0;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const double x = exp((double)l[a] - (double)m);
+    const double q = T.rsum[col[a]] + ev[a] * T.keepw[col[a]];
+    den += x;
+    num = __builtin_fma(x, q, num);
+  }
+  va[curo + pos + G2 * e] = num / den;
+}
+
+// Exact expected return of a tabular agent's own policy: k_optimal_return's recursion with
+//   v_t(s) = sum_a pi_t(a|s) q(s, a),   pi_t(.|s) = softmax(theta[s] + fl(fl(t * 0.001) * theta[D-1]))
+// in place of the max.  The logits are formed in f32 by actor_probs5's two rounded operations; the softmax and the
+// backup are f64.  One workgroup per (level, table) pair with the setup, work order and outcome loop above.  Work item
+// w belongs to thread w % blockDim at every step, so a thread reads the theta rows of its first ITEMS items once,
+// before the time loop, and keeps them in registers (the item loop is unrolled over ITEMS, so the rows are not
+// runtime-indexed).  Every mode's table has at most 6 items per thread and runs with MORE = false: theta is not read
+// inside the time loop.  MORE = true serves larger tables, which no mode has: the items past the first ITEMS go
+// through a plain loop that reads their rows from global memory at every step.
+template <int ITEMS, bool MORE>
+__global__ __launch_bounds__(1024) void k_policy_return(const int* __restrict__ levels,
+                                                        const float* __restrict__ theta, int D, int max_grid,
+                                                        int n_max, int L, float* __restrict__ v0,
+                                                        float* __restrict__ v_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+  const double* va = T.va;
+  const int G2 = T.G2, S = T.S, H = T.H;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int ncell = T.ncell;
+  const int nwork = ncell * T.ne;      // <= S; <= ITEMS * blockDim without MORE (the host's choice of ITEMS)
+
+  const float* th = theta + (size_t)blockIdx.x * D * 5;
+  float last[5];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) last[a] = th[(size_t)(D - 1) * 5 + a];
+  int st[ITEMS];          // pos | e << 8 of the thread's item k, -1 past the level's work
+  float row[ITEMS][5];
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) {
+    const int w = tid + k * nt;
+    st[k] = -1;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) row[k][a] = 0.0f;
+    if (w < nwork) {
+      const int ei = w / ncell;
+      const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
+      st[k] = pos | (e << 8);
+      const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
+#pragma unroll
+      for (int a = 0; a < 5; ++a) row[k][a] = r[a];
+    }
+  }
+
+  int curo = 0;    // v_t, written
+  int nxo = S;     // v_{t+1}, read
+  for (int t = H - 1; t >= 0; --t) {
+    const float c = __fmul_rn((float)t, 0.001f);
+    float tl[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) tl[a] = __fmul_rn(c, last[a]);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      if (st[k] < 0) continue;
+      float l[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
+      policy_backup(T, nxo, curo, st[k] & 0xFF, st[k] >> 8, l);
+    }
+    if (MORE) {
+      for (int w = tid + ITEMS * nt; w < nwork; w += nt) {
+        const int ei = w / ncell;
+        const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
+        const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
+        float l[5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(r[a], tl[a]);
+        policy_backup(T, nxo, curo, pos, e, l);
+      }
+    }
+    lds_barrier();
+    if (v_all != nullptr) {
+      float* out = v_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) out[s] = (float)va[curo + s];
+    }
+    const int sw = curo; curo = nxo; nxo = sw;
+  }
+  if (tid == 0) v0[blockIdx.x] = H > 0 ? (float)va[nxo + T.lev[L_START] + G2 * T.used] : 0.0f;
+}
+
+template <int ITEMS, bool MORE>
+int launch_policy_return(int n, int block, size_t lds, hipStream_t stream, const int* levels, const float* theta, int D,
+                         int max_grid, int n_max, int L, float* v0, float* v_all) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_return<ITEMS, MORE>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
+                  "toued_policy_return: cannot raise the dynamic LDS limit");
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((k_policy_return<ITEMS, MORE>), dim3(n), dim3(block), lds, stream, levels, theta, D, max_grid,
+                     n_max, L, v0, v_all);
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -229,6 +401,36 @@ int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int 
                      v0, v_all);
   TOUED_CHECK_LAUNCH();
   return 0;
+}
+
+int toued_policy_return(const int* levels, const float* theta, int n, int D, int max_grid, int n_max, int tabular,
+                        int max_rollout_len, float* v0, float* v_all, hipStream_t stream) {
+  TOUED_REQUIRE(tabular != 0, "toued_policy_return: non-tabular environments are unsupported (the agent is not a "
+                "table over the environment's states)");
+  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_policy_return: n=%d max_rollout_len=%d must be >= 0", n,
+                max_rollout_len);
+  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_policy_return: max_grid=%d outside [1, 16]", max_grid);
+  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_policy_return: n_max=%d outside [0, %d]", n_max,
+                TOUED_MAX_OBJS);
+  const int G2 = max_grid * max_grid;
+  const int S = G2 << n_max;
+  TOUED_REQUIRE(D == S + 1, "toued_policy_return: D=%d is not max_grid^2 * 2^n_max + 1 = %d", D, S + 1);
+  const size_t lds = optret_lds_bytes(G2, n_max);
+  TOUED_REQUIRE(lds <= kOptretLdsMax, "toued_policy_return: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)",
+                max_grid, n_max, lds, kOptretLdsMax);
+  if (n == 0) return 0;
+  // k_optimal_return's block size; the kernel is instantiated for the work items a thread can then own, and once
+  // more for the tables past six items per thread
+  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
+  const int items = (S + block - 1) / block;
+#define TOUED_POLRET_LAUNCH(I, MORE) \
+  launch_policy_return<I, MORE>(n, block, lds, stream, levels, theta, D, max_grid, n_max, max_rollout_len, v0, v_all)
+  if (items <= 1) return TOUED_POLRET_LAUNCH(1, false);
+  if (items <= 2) return TOUED_POLRET_LAUNCH(2, false);
+  if (items <= 4) return TOUED_POLRET_LAUNCH(4, false);
+  if (items <= 6) return TOUED_POLRET_LAUNCH(6, false);      // every mode's table
+  return TOUED_POLRET_LAUNCH(4, true);
+#undef TOUED_POLRET_LAUNCH
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@ from .rollout import RolloutWrapper
 SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
 SCORE_TRANSFORMS = ["proportional", "rank"]
+REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
 
 
 @dataclass
@@ -77,6 +78,13 @@ class LevelSampler:
         if args.score_function in VALUE_LOSS_FUNCTIONS and args.use_es:
             raise ValueError(f"Level score function {args.score_function} needs the agents' value critics, which "
                              f"--use_es does not train")
+        self.regret_eval = getattr(args, "regret_eval", "sampled")
+        if self.regret_eval not in REGRET_EVALS:
+            raise ValueError(f"regret_eval {self.regret_eval} not in {REGRET_EVALS}")
+        if self.regret_eval == "exact" and not (args.score_function in ("alg_regret", "optimal_regret")
+                                                and self.spec.tabular):
+            raise ValueError(f"regret_eval exact needs score_function alg_regret or optimal_regret and a tabular "
+                             f"environment mode (got {args.score_function}, {self.env_mode})")
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
         if args.score_function not in SCORE_FUNCTIONS:

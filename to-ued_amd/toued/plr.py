@@ -16,6 +16,11 @@ value critic (toued_value_loss_scores), no antagonist; the rest is unchanged.
 With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
 exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
 
+With ``--regret_eval exact`` (tabular modes; not in the reference) the two regret scores evaluate an agent by the exact
+expected return of its policy (toued_policy_return) in place of the eval rollouts: ``optimal_regret`` is V* - V^pi,
+deterministic and key-free, and ``alg_regret`` trains its antagonists on the same keys and returns
+V^pi(A2C) - V^pi(LPG).  The default, ``sampled``, is the code path above, bit for bit.
+
 Multi-GPU: the buffer is replicated on every rank and updated identically; each rank scores
 its own agents and the per-agent (term, score, buffer id) vectors are all-gathered, so every
 rank runs the same single-workgroup sampler kernel on the same inputs.
@@ -79,6 +84,12 @@ def algorithmic_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_th
     rng, tr = _split2(rng)
     step = torch.zeros(n, dtype=torch.int32, device=keys.device)
     lpg_rng, a2c_rng = _split2(rng)
+    if sampler.regret_eval == "exact":
+        # the antagonists train on the keys above, without the eval draws (no eval rollout follows); then both
+        # agents' exact returns in one launch
+        sampler.a2c_trainer().train(tr, theta, vcrit, step, levels, state, sampler.max_lifetime)
+        r = ro.policy_return(torch.cat([levels, levels]), torch.cat([lpg_theta, theta]), ro.eval_rollout_len)
+        return r[n:] - r[:n]
     # both eval_agent calls as one batch of 2n agents (each agent's rollout depends only on its own key, level and
     # table: bit-identical to two calls, at about the latency of one -- the returns-only rollout is latency-bound).
     # eval_agent's keys, reset and draws do not depend on the tables: the draws are made beside the antagonist's
@@ -110,6 +121,9 @@ def optimal_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta:
     if n == 0:
         return torch.zeros(0, device=keys.device)
     ro = sampler.rollout_manager
+    if sampler.regret_eval == "exact":      # V* - V^pi: no keys, no rollout, >= 0 up to the two tables' rounding
+        return ro.optimal_return(levels, ro.eval_rollout_len) - ro.policy_return(levels, lpg_theta,
+                                                                                 ro.eval_rollout_len)
     rng, _ = _split2(keys)
     rng, _ = _split2(rng)
     lpg_rng, _ = _split2(rng)

@@ -213,6 +213,33 @@ class RolloutWrapper:
                   int(self.spec.tabular), L, _lib.ptr(v0), _lib.ptr(v_all), _lib.stream_ptr())
         return v_all if return_all else v0
 
+    def policy_return(self, levels: torch.Tensor, theta: torch.Tensor, max_rollout_len: int,
+                      return_all: bool = False) -> torch.Tensor:
+        """The exact expected return of tabular agents' own policies over ``max_rollout_len`` steps
+        (toued_policy_return, no host synchronisation): ``optimal_return``'s recursion with the expectation over the
+        actor's softmax policy in place of the max.  With ``max_rollout_len = eval_rollout_len`` it is the expectation
+        of ``eval_agent``'s per-worker return.  Not in the reference.
+
+        levels int32 [n, 80], theta f32 [n, obs_dim, 5] -> f32 [n]; ``return_all``: f32 [n, max_rollout_len, S] with
+        S = obs_dim - 1, the masks of ``optimal_return``'s table.  A single level [80] with theta [obs_dim, 5] returns
+        a 0-d tensor, or [max_rollout_len, S].  Non-tabular modes raise NotImplementedError."""
+        if not self.spec.tabular:
+            raise NotImplementedError("Policy return not implemented for non-tabular environments.")
+        if levels.dim() == 1:
+            return self.policy_return(levels.view(1, -1), theta.unsqueeze(0), max_rollout_len, return_all)[0]
+        n, L = levels.shape[0], int(max_rollout_len)
+        if tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32 \
+                or theta.device != levels.device:
+            raise ValueError(f"policy_return: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, expected "
+                             f"float32 {(n, self.obs_dim, 5)} on {levels.device}")
+        S = self.obs_dim - 1
+        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
+        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
+        _lib.call("toued_policy_return", _lib.ptr(levels), _lib.ptr(theta), n, self.obs_dim,
+                  self.spec.max_grid_size, self.spec.max_n_objs, int(self.spec.tabular), L, _lib.ptr(v0),
+                  _lib.ptr(v_all), _lib.stream_ptr())
+        return v_all if return_all else v0
+
     def value_loss_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float, gae_lambda: float,
                           return_adv: bool = False):
         """The value-loss PLR scores of N agents' trajectories under their value critics ``vcrit`` f32 [N, D]
