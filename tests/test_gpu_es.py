@@ -69,6 +69,7 @@ def test_es_tell_matches_oracle(opt):
 
 
 def test_gru_fwd_multi_per_candidate():
+    from gru_ref import gru_forward_ref
     from toued import _lib
     from toued.lpg import LPGLayout, init_lpg_params
     C, W, T, F = 3, 64, 20, 7
@@ -94,19 +95,8 @@ def test_gru_fwd_multi_per_candidate():
         P = olpg.unflatten(torch.tensor(etas[c].cpu().numpy(), dtype=torch.float64), F)
         x = torch.tensor(X[:, :, c * W:(c + 1) * W].cpu().numpy(), dtype=torch.float64).permute(2, 1, 0)
         d = torch.tensor(done[c].T.astype(bool))
-        h = torch.zeros(W, 256, dtype=torch.float64)
-        outs = [None] * T
-        for t in reversed(range(T)):
-            h = torch.where(d[:, t, None], torch.zeros_like(h), h)
-            xt = x[:, t]
-            rg = torch.sigmoid(xt @ P["ir_w"] + P["ir_b"] + h @ P["hr_w"])
-            zg = torch.sigmoid(xt @ P["iz_w"] + P["iz_b"] + h @ P["hz_w"])
-            ng = torch.tanh(xt @ P["in_w"] + P["in_b"] + rg * (h @ P["hn_w"] + P["hn_b"]))
-            h = (1 - zg) * ng + zg * h
-            outs[t] = h
-        hs = torch.relu(torch.stack(outs, 1))
-        pi_ref = (hs @ P["pi_w"] + P["pi_b"])[..., 0]
-        y_ref = torch.softmax(hs @ P["y_w"] + P["y_b"], -1)
+        ref = gru_forward_ref(P, x, d, torch.float64)
+        pi_ref, y_ref = ref["pi_hat"], ref["y_hat"]
         np.testing.assert_allclose(pi_hat[:, c * W:(c + 1) * W].cpu().numpy().T, pi_ref.numpy(), atol=5e-6, rtol=0)
         np.testing.assert_allclose(y_hat[:, :, c * W:(c + 1) * W].cpu().numpy().transpose(2, 0, 1), y_ref.numpy(),
                                    atol=5e-6, rtol=0)

@@ -202,29 +202,15 @@ def test_gru_forward_matches_oracle():
     y_hat = torch.zeros(K, T, 8, R, device="cuda")
     gru.forward(0, X, torch.from_numpy(done[0]).cuda(), eta, pi_hat, y_hat)
     torch.cuda.synchronize()
-    # oracle: run the GRU core with x given directly
+    # oracle: the GRU core with x given directly (tests/gru_ref.py)
+    from gru_ref import gru_forward_ref
     P = olpg.unflatten(torch.tensor(eta.cpu().numpy(), dtype=torch.float64), 5)
     x = torch.tensor(X[:, 0].cpu().numpy(), dtype=torch.float64).permute(2, 1, 0)   # [R, T, F]
     d = torch.tensor(done[0].transpose(0, 2, 1).reshape(R, T).astype(bool))
-    h = torch.zeros(R, 256, dtype=torch.float64)
-    outs = [None] * T
-    saved = {"hin": [None] * T, "r": [None] * T, "z": [None] * T, "n": [None] * T}
-    for t in reversed(range(T)):
-        h = torch.where(d[:, t, None], torch.zeros_like(h), h)
-        xt = x[:, t]
-        rg = torch.sigmoid(xt @ P["ir_w"] + P["ir_b"] + h @ P["hr_w"])
-        zg = torch.sigmoid(xt @ P["iz_w"] + P["iz_b"] + h @ P["hz_w"])
-        hn = h @ P["hn_w"] + P["hn_b"]
-        ng = torch.tanh(xt @ P["in_w"] + P["in_b"] + rg * hn)
-        saved["hin"][t], saved["r"][t], saved["z"][t], saved["n"][t] = h, rg, zg, ng
-        saved.setdefault("hn", [None] * T)[t] = hn
-        h = (1 - zg) * ng + zg * h
-        outs[t] = h
-    hs = torch.relu(torch.stack(outs, 1))
-    pi_ref = (hs @ P["pi_w"] + P["pi_b"])[..., 0]
-    y_ref = torch.softmax(hs @ P["y_w"] + P["y_b"], -1)
-    np.testing.assert_allclose(pi_hat[0].cpu().numpy().T, pi_ref.numpy(), atol=5e-6, rtol=0)
-    np.testing.assert_allclose(y_hat[0].cpu().numpy().transpose(2, 0, 1), y_ref.numpy(), atol=5e-6, rtol=0)
+    ref = gru_forward_ref(P, x, d, torch.float64)
+    saved = {"hin": ref["h_in"], "r": ref["r"], "z": ref["z"], "n": ref["n"], "hn": ref["hn"]}      # [R, T, 256]
+    np.testing.assert_allclose(pi_hat[0].cpu().numpy().T, ref["pi_hat"].numpy(), atol=5e-6, rtol=0)
+    np.testing.assert_allclose(y_hat[0].cpu().numpy().transpose(2, 0, 1), ref["y_hat"].numpy(), atol=5e-6, rtol=0)
     # the saves the backward reads: [unit][column t*R + r]
     def tr(a):
         return a.reshape(256, T, R).transpose(1, 2, 0)
@@ -235,7 +221,7 @@ def test_gru_forward_matches_oracle():
     if not _lib.lib().toued_gru_bwd_col_exp(R):
         saves.append(("n", tr(gru.S[2].cpu().numpy())))
     for name, arr in saves:
-        ref = np.stack([saved[name][t].numpy() for t in range(T)])
+        ref = saved[name].numpy().transpose(1, 0, 2)     # [T, R, 256]
         np.testing.assert_allclose(arr, ref, atol=5e-6 * (1 + np.abs(ref).max()), rtol=0, err_msg=name)
 
 

@@ -13,12 +13,14 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "to-ued_amd"))
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))   # gru_ref: the float64 restatement the tests use
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
 def main():
+    from gru_ref import gru_forward_ref
     from oracle import lpg as olpg
     from toued.lpg import LPGGRU, LPGLayout, init_lpg_params
     N, W, T, K = 4, 64, 20, 1
@@ -39,22 +41,10 @@ def main():
     P = olpg.unflatten(torch.tensor(eta.cpu().numpy(), dtype=torch.float64), 5)
     x = torch.tensor(X[:, 0].cpu().numpy(), dtype=torch.float64).permute(2, 1, 0)
     d = torch.tensor(done[0].transpose(0, 2, 1).reshape(R, T).astype(bool))
-    h = torch.zeros(R, 256, dtype=torch.float64)
-    outs, hins = [None] * T, [None] * T
-    for t in reversed(range(T)):
-        h = torch.where(d[:, t, None], torch.zeros_like(h), h)
-        xt = x[:, t]
-        rg = torch.sigmoid(xt @ P["ir_w"] + P["ir_b"] + h @ P["hr_w"])
-        zg = torch.sigmoid(xt @ P["iz_w"] + P["iz_b"] + h @ P["hz_w"])
-        ng = torch.tanh(xt @ P["in_w"] + P["in_b"] + rg * (h @ P["hn_w"] + P["hn_b"]))
-        hins[t] = h
-        h = (1 - zg) * ng + zg * h
-        outs[t] = h
-    hs = torch.relu(torch.stack(outs, 1))
-    pi_ref = (hs @ P["pi_w"] + P["pi_b"])[..., 0].numpy()
-    y_ref = torch.softmax(hs @ P["y_w"] + P["y_b"], -1).numpy()
+    ref = gru_forward_ref(P, x, d, torch.float64)
+    pi_ref, y_ref = ref["pi_hat"].numpy(), ref["y_hat"].numpy()
     hin_gpu = gru.hin_rows().cpu().numpy().reshape(256, T, R).transpose(2, 1, 0)
-    hin_ref = torch.stack(hins, 1).numpy()
+    hin_ref = ref["h_in"].numpy()
     res = {"kernel": "f32" if os.environ.get("TOUED_GRU_F32") == "1" else "default",
            "pi_hat_max_abs": float(np.abs(pi_hat[0].cpu().numpy().T - pi_ref).max()),
            "y_hat_max_abs": float(np.abs(y_hat[0].cpu().numpy().transpose(2, 0, 1) - y_ref).max()),
