@@ -107,6 +107,23 @@ int toued_level_gen(const void* program, const uint32_t* keys, const int* buffer
 /* only the levels i with mask[i] != 0 are written (in place: the level sampler's where(terminated, new, old)) */
 int toued_level_gen_masked(const void* program, const uint32_t* keys, const int* buffer_ids, int* levels_out, int n,
                            const uint8_t* mask, hipStream_t stream);
+/* ACCEL level editing (Parker-Holder et al. 2022; not in the reference) of n reset slots.  levels_inout [n][80] holds
+ * the generator's level of each slot and keys [n][2] the generator keys.  Row j: ek = fold_in(keys[j], 0x45444954);
+ * ek_use, ek_edit = split(ek); if uniform(ek_use) < p_edit and parent_ids[j] >= 0 the row becomes
+ * edit(buffer_levels[parent_ids[j]], ek_edit) with the incoming row's buffer id, and edited_out[j] (nullable) = 1;
+ * otherwise the row is untouched and edited_out[j] = 0.  edit applies num_edits edits; each consumes
+ * rng, k_op = split(rng); rng, k_cell = split(rng); rng, k_obj = split(rng); rng, k_val = split(rng) whatever it does:
+ * op = the randint(k_op, 0, popcount(ops_mask))-th set bit of ops_mask, c = randint(k_cell, 0, grid^2),
+ * o = randint(k_obj, 0, max(n_objs, 1)), dv = uniform(k_val, -reward_delta, reward_delta).  With "occupied" = the
+ * start cell or one of the max_n_objs static object cells: bit 0 toggles wall c unless occupied; bit 1 moves object o
+ * to c unless n_objs == 0, c is a wall or occupied; bit 2 moves the start to c unless c is a wall or occupied; bit 3
+ * sets the per-type reward of object o's type t to clamp(r + dv, t == 0 ? 0 : -1, 1) and re-resolves the per-object
+ * rewards, unless n_objs == 0.  Every other field is the parent's.  -1 for negative n or num_edits, ops_mask outside
+ * [1, 15], p_edit outside [0, 1], max_n_objs outside [0, TOUED_MAX_OBJS], max_n_types outside [1, TOUED_MAX_TYPES];
+ * n == 0 succeeds. */
+int toued_level_edit(const int* buffer_levels, const int* parent_ids, const uint32_t* keys, int n, int max_n_objs,
+                     int max_n_types, float p_edit, int num_edits, int ops_mask, float reward_delta,
+                     int* levels_inout, uint8_t* edited_out, hipStream_t stream);
 
 /* ---- gymnax Environment plugin API (GridWorld, gridworld.py:72-211) ----
  * Worker i uses levels[i / W]; keys are per worker. */
@@ -186,6 +203,11 @@ int toued_choice_cdf(const uint32_t* key, const float* cdf, int B, int n, int* o
  * stable, jax float order.  Flags are bool (uint8) arrays of length B <= 8192. */
 int toued_plr_reset_ids(int B, int N, const float* score, const uint8_t* active, const uint8_t* fresh, int* ids,
                         hipStream_t stream);
+/* The level editor's parents (not in the reference): slot b is eligible if !fresh[b] and b is not among
+ * reset_ids[0..N); order = stable argsort(where(eligible, -score, +inf)) in jax float order; parent_ids[j] =
+ * order[j % n_elig], or -1 when no slot is eligible.  Active slots are eligible.  One workgroup, B <= 8192. */
+int toued_plr_parent_ids(int B, int N, const float* score, const uint8_t* fresh, const int* reset_ids,
+                         int* parent_ids, hipStream_t stream);
 /* alg_regret selection (:203-227) on the buffer after the terminated-level update.
  * keys[3][2] = {replay_rng, random_rng, rng} from `rng, replay_rng, random_rng = split(rng, 3)`.
  * Outputs (int32[N]): chosen = where(use, replay, random), replay (_replay_from_buffer :355-390,

@@ -127,6 +127,21 @@ TOUED_DEV float uniform_from_bits(uint32_t bits, float lo, float hi) {
   return fmaxf(lo, __fadd_rn(__fmul_rn(f, __fsub_rn(hi, lo)), lo));
 }
 
+TOUED_DEV uint32_t mulmod_span(uint32_t span) {
+  uint32_t m = 65536u % span;
+  return (m * m) % span;
+}
+
+// jax.random.randint(key, (), 0, span) (the level generator and the level editor)
+TOUED_DEV int randint0(uint2 key, uint32_t span) {
+  uint2 k1, k2;
+  split2(key, k1, k2);
+  const uint32_t hb = bits1(k1), lb = bits1(k2);
+  if (span == 0u) span = 1u;
+  const uint32_t off = ((hb % span) * mulmod_span(span) + (lb % span)) % span;
+  return (int)off;
+}
+
 // ----------------------------------------------------------------------------
 // Portable math (oracle/pmath.py)
 TOUED_DEV float pow2i(int k) { return __uint_as_float((uint32_t)(k + 127) << 23); }

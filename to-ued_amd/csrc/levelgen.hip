@@ -36,21 +36,6 @@ struct ModeProgram {
   ModeSpec sub[10];
 };
 
-TOUED_DEV uint32_t mulmod_span(uint32_t span) {
-  uint32_t m = 65536u % span;
-  return (m * m) % span;
-}
-
-// jax.random.randint(key, (), 0, span)
-TOUED_DEV int randint0(uint2 key, uint32_t span) {
-  uint2 k1, k2;
-  split2(key, k1, k2);
-  const uint32_t hb = bits1(k1), lb = bits1(k2);
-  if (span == 0u) span = 1u;
-  const uint32_t off = ((hb % span) * mulmod_span(span) + (lb % span)) % span;
-  return (int)off;
-}
-
 TOUED_DEV int log_uniform_int(uint2 key, float lo, float hi) {
   const float u = uniform_from_bits(bits1(key), plog(lo), plog(hi));
   return (int)rintf(pexp(u));

@@ -8,6 +8,8 @@
 //   k_plr_sample     _replay_from_buffer (:363-385, rank or proportional), _sample_random_from_buffer
 //                    (:396-407), and the replay/random selection (:212-227): bernoulli count, the
 //                    n_replayable guard, permutation(use_replay), where(use, replay, random)
+//   k_plr_parent_ids the level editor's parents (not in the reference): the scored slots that this round does not
+//                    reset, highest score first, dealt round-robin to the reset slots
 #include "common.h"
 
 namespace {
@@ -193,6 +195,37 @@ __global__ void __launch_bounds__(kThreads) k_plr_sample(int B, int N, const flo
   (void)rng2;
 }
 
+// parent_ids[j] = order[j % n_elig] with order = argsort(where(eligible, -score, +inf)), eligible = !fresh and not
+// among reset_ids[0..N); -1 when nothing is eligible.  A reset id outside [0, B) excludes nothing.
+__global__ void __launch_bounds__(kThreads) k_plr_parent_ids(int B, int N, const float* __restrict__ score,
+                                                             const uint8_t* __restrict__ fresh,
+                                                             const int* __restrict__ reset_ids,
+                                                             int* __restrict__ parent_ids) {
+  __shared__ uint64_t s[kMaxSort];
+  __shared__ float f[kMaxSort];
+  __shared__ uint8_t elig[kMaxSort];
+  __shared__ int red[16];
+  const int P = pow2_ceil(B);
+  const int tid = threadIdx.x;
+  for (int i = tid; i < B; i += blockDim.x) elig[i] = fresh[i] ? 0 : 1;
+  __syncthreads();
+  for (int j = tid; j < N; j += blockDim.x) {
+    const int r = reset_ids[j];
+    if (r >= 0 && r < B) elig[r] = 0;     // duplicates store the same byte
+  }
+  __syncthreads();
+  int n_elig = 0;
+  for (int base = 0; base < B; base += blockDim.x) {
+    const int i = base + tid;
+    n_elig += block_count(i < B && elig[i], red);
+  }
+  for (int i = tid; i < B; i += blockDim.x) f[i] = elig[i] ? -score[i] : __builtin_inff();
+  __syncthreads();
+  fill_keys(s, B, P, f);
+  bitonic(s, P);
+  for (int j = tid; j < N; j += blockDim.x) parent_ids[j] = n_elig ? (int)(uint32_t)s[j % n_elig] : -1;
+}
+
 extern "C" {
 
 int toued_plr_reset_ids(int B, int N, const float* score, const uint8_t* active, const uint8_t* fresh, int* ids,
@@ -213,6 +246,17 @@ int toued_plr_sample(int B, int N, const float* score, const uint8_t* active, co
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_plr_sample, dim3(1), dim3(kThreads), 0, stream, B, N, score, active, fresh, keys,
                      proportional, temperature, p_replay, chosen, rep, rnd, use_out);
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
+int toued_plr_parent_ids(int B, int N, const float* score, const uint8_t* fresh, const int* reset_ids,
+                         int* parent_ids, hipStream_t stream) {
+  TOUED_REQUIRE(B > 0 && B <= kMaxSort && N >= 0 && N <= B, "toued_plr_parent_ids: need 0 <= N <= B <= %d",
+                kMaxSort);
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(k_plr_parent_ids, dim3(1), dim3(kThreads), 0, stream, B, N, score, fresh, reset_ids,
+                     parent_ids);
   TOUED_CHECK_LAUNCH();
   return 0;
 }

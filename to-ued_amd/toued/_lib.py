@@ -41,6 +41,7 @@ _SIGS = {
     "toued_mode_program_bytes": [],
     "toued_level_gen": [_P, _P, _P, _P, _P, _I, _P],
     "toued_level_gen_masked": [_P, _P, _P, _P, _I, _P, _P],
+    "toued_level_edit": [_P, _P, _P, _I, _I, _I, _F, _I, _I, _F, _P, _P, _P],
     "toued_gw_reset": [EnvSpecC, _P, _I, _P, _P, _P, _P, _I, _P],
     "toued_gw_step": [EnvSpecC, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "toued_batch_reset": [EnvSpecC, _P, _P, _I, _I, _P, _P, _P, _P],
@@ -124,6 +125,7 @@ _SIGS = {
     "toued_es_grad": [_P, _P, _F, _P, _I, _L, _P, _P],
     "toued_es_opt": [_L, _I, _P, _P, _F, _P, _P, _F, _F, _F, _F, _F, _F, _P],
     "toued_plr_reset_ids": [_I, _I, _P, _P, _P, _P, _P],
+    "toued_plr_parent_ids": [_I, _I, _P, _P, _P, _P, _P],
     "toued_plr_sample": [_I, _I, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P],
     "toued_wgrad_workspace_floats": [_I, _I, _L],
     "toued_wgrad": [_I, _I, _L, _P, _L, _P, _L, _P, _P, ctypes.c_size_t, _P],

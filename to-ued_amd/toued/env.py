@@ -151,6 +151,52 @@ class LevelGenerator:
         return levels
 
 
+EDIT_OPS = ("walls", "objects", "start", "rewards")     # bit i of toued_level_edit's ops_mask
+
+
+def parse_edit_ops(ops) -> int:
+    """A comma list (or sequence) of EDIT_OPS names -> toued_level_edit's ops_mask; ValueError for an unknown name
+    or an empty list."""
+    names = [o.strip() for o in ops.split(",")] if isinstance(ops, str) else list(ops)
+    names = [o for o in names if o]
+    if not names:
+        raise ValueError(f"edit_ops is empty: give a comma list of {EDIT_OPS}")
+    mask = 0
+    for o in names:
+        if o not in EDIT_OPS:
+            raise ValueError(f"edit_ops: unknown op {o!r} (known: {EDIT_OPS})")
+        mask |= 1 << EDIT_OPS.index(o)
+    return mask
+
+
+class LevelEditor:
+    """Device ACCEL editor (toued_level_edit; not in the reference): with probability ``p_edit`` a reset slot's
+    generated level is replaced by ``num_edits`` small edits (``ops``: wall toggles, object moves, start moves,
+    per-type reward nudges of at most ``reward_delta``) of a parent level from the buffer."""
+
+    def __init__(self, spec: EnvSpec, ops="walls,objects,start", num_edits: int = 5, p_edit: float = 0.5,
+                 reward_delta: float = 0.1):
+        self.spec = spec
+        self.ops_mask = parse_edit_ops(ops)
+        if num_edits < 0:
+            raise ValueError(f"num_edits {num_edits} is negative")
+        if not 0.0 <= p_edit <= 1.0:
+            raise ValueError(f"edit_prob {p_edit} outside [0, 1]")
+        self.num_edits, self.p_edit, self.reward_delta = int(num_edits), float(p_edit), float(reward_delta)
+
+    def __call__(self, buffer_levels: torch.Tensor, parent_ids: torch.Tensor, keys: torch.Tensor,
+                 levels: torch.Tensor) -> torch.Tensor:
+        """Edits ``levels`` int32[n, 80] (the generator's levels of ``keys`` int32[n, 2]) in place: row j becomes the
+        edited ``buffer_levels[parent_ids[j]]`` where the row's own coin says so and ``parent_ids[j] >= 0``.  Returns
+        the u8 [n] flags of the rows that were replaced."""
+        n = keys.shape[0]
+        edited = torch.empty((n,), dtype=torch.uint8, device=keys.device)
+        _lib.call("toued_level_edit", _lib.ptr(buffer_levels), _lib.ptr(parent_ids), _lib.ptr(keys.contiguous()), n,
+                  self.spec.max_n_objs, self.spec.max_n_obj_types, self.p_edit, self.num_edits, self.ops_mask,
+                  self.reward_delta, _lib.ptr(levels), _lib.ptr(edited), _lib.stream_ptr())
+        return edited
+
+
 class GridWorld:
     """gymnax ``Environment`` API for GridWorld (gridworld.py:38-236), vectorised.
 

@@ -9,6 +9,10 @@ with the mean of max(GAE, 0) / |GAE| of the agent's eval trajectory under its
 value critic; not with --use_es, not in the reference) and ``optimal_regret``
 (PLR with the true regret against the level's exact optimal return; tabular
 modes, not in the reference).
+Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
+with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
+refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
+level instead of a fresh draw of the generator (toued.plr.reset_lowest_scoring).
 All state is device-resident; per-agent work is
 computed for the whole batch and masked by ``terminated`` exactly like the
 reference's vmapped ``jnp.where`` (the masked-out work has no observable effect).
@@ -24,13 +28,14 @@ import torch
 from . import _lib, prng
 from .agents import (DENSE0_HASH, AgentBatch, AgentHyperparams, create_agents, create_agents_into,
                      create_value_critics, lecun_tables_into, lecun_tables_into_folded)
-from .env import L_BUFID, L_LIFETIME, LevelGenerator, get_env_spec
+from .env import L_BUFID, L_LIFETIME, LevelEditor, LevelGenerator, get_env_spec
 from .rollout import RolloutWrapper
 
 SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
 SCORE_TRANSFORMS = ["proportional", "rank"]
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
+LEVEL_EDITORS = ("none", "accel")        # --level_editor: refill reset slots from the generator, or by ACCEL edits
 
 
 @dataclass
@@ -85,6 +90,18 @@ class LevelSampler:
                                                 and self.spec.tabular):
             raise ValueError(f"regret_eval exact needs score_function alg_regret or optimal_regret and a tabular "
                              f"environment mode (got {args.score_function}, {self.env_mode})")
+        level_editor = getattr(args, "level_editor", "none")
+        if level_editor not in LEVEL_EDITORS:
+            raise ValueError(f"level_editor {level_editor} not in {LEVEL_EDITORS}")
+        self.editor = None
+        if level_editor == "accel":
+            if args.score_function in ("random", "frozen"):
+                raise ValueError(f"level_editor accel needs a score function with a reset round (got "
+                                 f"{args.score_function}, which never resets a buffer slot)")
+            self.editor = LevelEditor(self.spec, getattr(args, "edit_ops", "walls,objects,start"),
+                                      getattr(args, "num_edits", 5), getattr(args, "edit_prob", 0.5),
+                                      getattr(args, "edit_reward_delta", 0.1))
+        self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
         if args.score_function not in SCORE_FUNCTIONS:

@@ -51,14 +51,36 @@ def _split2(rng):
     return ks[..., 0, :].contiguous(), ks[..., 1, :].contiguous()
 
 
+def parent_ids(buffer, reset_ids: torch.Tensor) -> torch.Tensor:
+    """The level editor's parents for the reset slots ``reset_ids`` [N] (toued_plr_parent_ids): the buffer's scored
+    slots (not new, active ones included) outside ``reset_ids``, highest score first, dealt round-robin; -1 everywhere
+    when there is none.  Not in the reference."""
+    N = reset_ids.shape[0]
+    out = torch.empty(N, dtype=torch.int32, device=reset_ids.device)
+    _lib.call("toued_plr_parent_ids", len(buffer), N, _lib.ptr(buffer.score), _lib.ptr(buffer.new),
+              _lib.ptr(reset_ids.contiguous()), _lib.ptr(out), _lib.stream_ptr())
+    return out
+
+
 def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int) -> torch.Tensor:
-    """level_sampler.py:331-353, in place on ``buffer``; returns the reset ids [n_new]."""
+    """level_sampler.py:331-353, in place on ``buffer``; returns the reset ids [n_new].
+
+    With ``--level_editor accel`` (not in the reference) the generated levels then pass through the level editor:
+    a row whose coin (``--edit_prob``) says so becomes an edited copy of a parent, a scored buffer level read before
+    this round's copy and never one of the slots being reset; ``sampler.last_edit`` keeps the parents and the flags.
+    The generator still runs on the same keys and nothing else in the round changes.  Multi-GPU: both kernels read
+    only replicated state (the buffer and the rng), so every rank computes identical children and no collective is
+    needed."""
     B = len(buffer)
     ids = torch.empty(n_new, dtype=torch.int32, device=buffer.score.device)
     _lib.call("toued_plr_reset_ids", B, n_new, _lib.ptr(buffer.score), _lib.ptr(buffer.active),
               _lib.ptr(buffer.new), _lib.ptr(ids), _lib.stream_ptr())
     keys = prng.split(rng, n_new)
     levels = sampler.gen(keys, buffer_ids=ids)
+    editor = getattr(sampler, "editor", None)
+    if editor is not None:
+        parents = parent_ids(buffer, ids)
+        sampler.last_edit = {"parent": parents, "edited": editor(buffer.levels, parents, keys, levels)}
     il = ids.long()
     buffer.levels.index_copy_(0, il, levels)
     buffer.score.index_fill_(0, il, 0.0)
