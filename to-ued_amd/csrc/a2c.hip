@@ -731,21 +731,13 @@ __global__ void __launch_bounds__(256) k_a2c_chain(EnvSpec sp, const int* __rest
   float* vec = reinterpret_cast<float*>(key + A2C_SORT_MAX);                    // [W*T][6]
   const float* tab = theta + (size_t)a * D * 5;
   const float* v = vcrit + (size_t)a * D;
-  // env workers: all W in wave 0 (default), or spread over the four waves (A2C_ENV_SPREAD=1, W % 4 == 0: W/4 lanes of
-  // each wave, so each wave's row gather touches W/4 cache lines instead of W).  The spread paid before the level's
-  // transition table (NPT); since, one wave per agent costs a quarter of the issue slots and the chain runs faster
-  // (profiles/r04/a2c_env_spread_r04z.txt: 93.2 vs 95.2 k cycles per update, 1.37 vs 1.50 ms per 32-update launch)
-#ifndef A2C_ENV_SPREAD
-#define A2C_ENV_SPREAD 0
-#endif
-  const bool spread = !SELF && A2C_ENV_SPREAD && W % 4 == 0;   // (SELF: the env chain in wave 0 always)
-  const int w = spread ? (tid >> 6) * (W / 4) + (tid & 63) : tid;
-  const bool env = spread ? (tid & 63) < W / 4 : tid < W;
+  // env workers: all W in wave 0.  (Spread over the four waves, W/4 lanes each, paid before the level's transition
+  // table (NPT); since, one wave per agent costs a quarter of the issue slots and the chain runs faster:
+  // profiles/r04/a2c_env_spread_r04z.txt, 93.2 vs 95.2 k cycles per update, 1.37 vs 1.50 ms per 32-update launch)
+  const int w = tid;
+  const bool env = tid < W;
   const int i = a * W + w;
-#ifndef A2C_NPT
-#define A2C_NPT 1
-#endif
-  constexpr bool NPT = A2C_NPT && !CAND;   // the level's transition table in LDS (TrainWorker)
+  constexpr bool NPT = !CAND;   // the level's transition table in LDS (TrainWorker)
   TrainWorker<NMAX, CAND, NPT> wk;
   if (env) wk.init(sp, levels, a, theta, D, state, n, i);
   if constexpr (NPT) {   // the level's transition table after the update's LDS (toued_a2c_chain sizes it)
@@ -848,13 +840,7 @@ __global__ void __launch_bounds__(256) k_a2c_chain(EnvSpec sp, const int* __rest
       S.ix[T * W + w] = wk.idx;
       S.cc[T * W + w] = (float)wk.s.time * 0.001f;
     } else if (SELF && wv >= 1 && u + 1 < U) {
-#ifndef A2C_SELF_SPLIT
-#define A2C_SELF_SPLIT 1
-#endif
-      if (A2C_SELF_SPLIT)
-        make_draws_split(u + 1, (u + 1) & 1);   // beside wave 0's env chain
-      else
-        make_draws(u + 1, (u + 1) & 1, wv - 1, 3);
+      make_draws_split(u + 1, (u + 1) & 1);   // beside wave 0's env chain
     }
     if (u == U - 1) A2C_STAMP(7);
     __syncthreads();

@@ -12,7 +12,7 @@
 //   k_clip_dot     <G_k, adjoint> per agent -> clip-VJP coefficients
 //   k_hvp          Hessian-vector products of the actor/critic losses through the linear-softmax
 //                  (row-gather) parameterisation + cotangents on pi_hat / y_hat (+ L2 regularisers)
-//   k_embed_bwd    embedding-MLP parameter gradient from the GRU input cotangents
+//   k_embed_bwd3   embedding-MLP parameter gradient from the GRU input cotangents
 //   k_adam         optax scale_by_adam + scale(lr) + scale(-1)
 //
 // Sample index s = (a*T + t)*W + w (trajectory layout), GRU row r = a*W + w.
@@ -944,143 +944,11 @@ __global__ void __launch_bounds__(256) k_hvp(int N, int W, int T, int D, int K, 
 }
 
 // ---------------------------------------------------------------------------- embedding MLP backward
-#ifndef EMBED_V
-#define EMBED_V 3   // k_embed_bwd3 (one lane per sample, e1_w / e1_b on the matrix cores); 1: k_embed_bwd
-#endif
 #ifndef EMBED_WPE
 #define EMBED_WPE 3   // k_embed_bwd3's waves per SIMD (its register budget: 512 / EMBED_WPE)
 #endif
 // grad layout (161 floats): e1_b[16], e1_w[8*16], e2_b[1], e2_w[16] (flat-eta order within MLP_0)
 // Inputs: y_t / y_tp1 recomputed from phi_k; cotangents dX3 (pyt), dX4 (pyt1, masked by done).
-// Four lanes per sample, each owning four of the 16 hidden units (41 accumulators per lane instead of 161:
-// occupancy); the quad recomputes the sample's critic output y.  Lane sums are reduced over the 16 samples
-// of a wave with cross-lane adds, then over the block; partial[block][161] in the flat layout below.
-template <bool UNIF>
-__global__ void __launch_bounds__(256) k_embed_bwd(int N, int W, int T, int D, int K, const float* __restrict__ phi_hist,
-                                                   long phi_stride, int phi_slot0, const int* __restrict__ tidx_hist, long tidx_stride,
-                                                   const int* __restrict__ ttime_hist, const uint8_t* __restrict__ tdone_hist,
-                                                   long tstep_stride, const float* __restrict__ dX3,
-                                                   const float* __restrict__ dX4, long dx_stride_k,
-                                                   const float* __restrict__ e1w, const float* __restrict__ e1b,
-                                                   const float* __restrict__ e2w, float* __restrict__ partial) {
-  const int q = threadIdx.x & 3;                 // hidden units 4q .. 4q+3
-  float w1[8][4], b1[4], w2[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    b1[u] = e1b[4 * q + u];
-    w2[u] = e2w[4 * q + u];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w1[i][u] = e1w[i * 16 + 4 * q + u];
-  }
-  float aw[8][4], ab[4], a2[4], ac = 0.0f;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    ab[u] = 0.0f; a2[u] = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) aw[i][u] = 0.0f;
-  }
-  // sample indices fit 31 bits (checked by the launcher): 32-bit index maths, no 64-bit divisions
-  const int NTW = N * T * W;
-  const int total = K * NTW;
-  const int R = N * W;
-  const int nthr = gridDim.x * (blockDim.x >> 2);
-  // a sample's loads that do not depend on its observation rows: issued one sample ahead (the clamped index keeps
-  // the prefetch unconditional, so the wait counts stay per load)
-  struct In {
-    const float* ph;
-    int ix[2];
-    float cx[2], cg[2], lastC[8];
-  };
-  auto load_in = [&](int g) {
-    In v;
-    const int k = (unsigned)g / (unsigned)NTW;
-    const int s = g - k * NTW;
-    const int at = (unsigned)s / (unsigned)W;
-    const int w = s - at * W;
-    const int a = (unsigned)at / (unsigned)T;
-    const int t = at - a * T;
-    const int r = a * W + w;
-    const int* tidx = tidx_hist + k * tidx_stride;
-    const int* ttime = ttime_hist + k * tidx_stride;
-    const uint8_t* tdone = tdone_hist + k * tstep_stride;
-    const int slot = k + phi_slot0 > K ? k + phi_slot0 - (K + 1) : k + phi_slot0;   // ring of K + 1 slots
-    v.ph = phi_hist + slot * phi_stride + (size_t)a * D * 8;
-    const size_t o0 = ((size_t)a * (T + 1) + t) * W + w;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v.lastC[j] = v.ph[(size_t)(D - 1) * 8 + j];
-    const size_t o = (size_t)k * dx_stride_k + (size_t)t * R + r;
-    v.ix[0] = tidx[o0];
-    v.ix[1] = tidx[o0 + W];
-    v.cx[0] = (float)ttime[o0] * 0.001f;
-    v.cx[1] = (float)ttime[o0 + W] * 0.001f;
-    v.cg[0] = dX3[o];
-    v.cg[1] = tdone[s] ? 0.0f : dX4[o];
-    return v;
-  };
-  const int g0 = blockIdx.x * (blockDim.x >> 2) + (threadIdx.x >> 2);
-  In nx = load_in(min(g0, total - 1));
-  for (int g = g0; g < total; g += nthr) {
-    const In cur = nx;
-    nx = load_in(min(g + nthr, total - 1));
-    const float* ph = cur.ph;
-    const int (&ix)[2] = cur.ix;
-    const float (&cx)[2] = cur.cx;
-    const float (&cgs)[2] = cur.cg;
-    const float (&lastC)[8] = cur.lastC;
-    // both observations' row gathers issued before either is used (two independent chains per sample)
-    float ys[2][8];
-#pragma unroll
-    for (int which = 0; which < 2; ++which) probs_of<8>(ph, lastC, ix[which], cx[which], ys[which]);
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-      const float cg = cgs[which];
-      if (cg == 0.0f) continue;
-      const float (&y)[8] = ys[which];
-      if (q == 0) ac += cg;  // e2_b
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float pre = b1[u];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) pre += y[i] * w1[i][u];
-        const float hid = fmaxf(pre, 0.0f);
-        a2[u] += hid * cg;                               // e2_w
-        const float dh = pre > 0.0f ? w2[u] * cg : 0.0f;
-        ab[u] += dh;                                     // e1_b
-#pragma unroll
-        for (int i = 0; i < 8; ++i) aw[i][u] += y[i] * dh;   // e1_w
-      }
-    }
-  }
-  // lanes with the same q: sum over the wave's 16 samples (xor 4, 8, 16, 32), then over the block's waves
-  auto qsum = [](float v) {
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
-  __shared__ float red[4][161];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int h = 4 * q + u;
-    const float vb = qsum(ab[u]), v2 = qsum(a2[u]);
-    if (lane < 4) { red[wv][h] = vb; red[wv][145 + h] = v2; }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float vw = qsum(aw[i][u]);
-      if (lane < 4) red[wv][16 + i * 16 + h] = vw;
-    }
-  }
-  {
-    const float vc = qsum(ac);
-    if (lane == 0) red[wv][144] = vc;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 161; i += blockDim.x) {
-    float v = 0.0f;
-    for (int qq = 0; qq < (int)(blockDim.x >> 6); ++qq) v += red[qq][i];
-    partial[(size_t)blockIdx.x * 161 + i] = v;
-  }
-}
 
 // probs_of on a row already in registers (the same operations in the same order: bit-identical)
 template <int K>
@@ -1103,15 +971,15 @@ TOUED_DEV void probs_regs(const float* row, const float* last, float c, float* p
   for (int j = 0; j < K; ++j) p[j] *= inv;
 }
 
-// The same gradient with one lane per sample and the e1_w / e1_b reduction on the matrix cores.  A wave takes 64
-// consecutive samples per round (each load instruction covers 64 samples: 256 contiguous bytes of an index or
-// cotangent array, where k_embed_bwd's quad-per-sample layout covered 16 and repeated the loads and the softmax in
-// four lanes); a lane computes its sample's critic outputs y and, per observation, the 16 hidden units (e1_w / e1_b /
+// One lane per sample and the e1_w / e1_b reduction on the matrix cores; partial[block][161] in the flat layout above.
+// A wave takes 64 consecutive samples per round (each load instruction covers 64 samples: 256 contiguous bytes of an
+// index or cotangent array; a quad-per-sample layout covered 16 and repeated the loads and the softmax in four lanes);
+// a lane computes its sample's critic outputs y and, per observation, the 16 hidden units (e1_w / e1_b /
 // e2_w broadcast from LDS: no per-lane weight registers), accumulates e2_w / e2_b itself, and writes the item's
 // rows a = [y, 1] and d = dh (the hidden cotangents) to the wave's LDS tile; sixteen v_mfma_f32_16x16x4_f32 then add
 // A^T D over the 64 items into a 16 x 16 accumulator (rows 0..7 e1_w, row 8 e1_b) -- 4 accumulator registers
 // instead of 41 per lane, so the kernel runs at 6 waves per SIMD.  The next round's index / time / cotangent loads
-// are issued before this round's maths.  f32 products and sums, in another order than k_embed_bwd.
+// are issued before this round's maths.  f32 products and sums.
 template <bool UNIF>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EMBED_WPE))) k_embed_bwd3(int N, int W, int T, int D, int K, const float* __restrict__ phi_hist,
                                                     long phi_stride, int phi_slot0, const int* __restrict__ tidx_hist, long tidx_stride,
@@ -2476,11 +2344,7 @@ int toued_embed_bwd(int N, int W, int T, int D, int K, const float* phi_hist, lo
                                    phi_slot0,                                                                       \
                                    tidx_hist, tidx_stride, ttime_hist, tdone_hist, tstep_stride, dX3, dX4, dx_stride_k, \
                                    e1w, e1b, e2w, partial)
-  if (EMBED_V == 3) {
-    if (W % 64 == 0) L_(k_embed_bwd3<true>); else L_(k_embed_bwd3<false>);
-  } else {
-    if (W % 64 == 0) L_(k_embed_bwd<true>); else L_(k_embed_bwd<false>);
-  }
+  if (W % 64 == 0) L_(k_embed_bwd3<true>); else L_(k_embed_bwd3<false>);
 #undef L_
   TOUED_CHECK_LAUNCH();
   return 0;

@@ -148,11 +148,6 @@ TOUED_DEV int lane_now() {
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
 }
-// x of lane l ^ 32, with the source lane re-derived here (__shfl_xor's lane arithmetic, kept live across the step loop
-// by the compiler, was spilled; its reload in the gate maths waited for every outstanding save store)
-TOUED_DEV float xor32(float x) {
-  return __int_as_float(__builtin_amdgcn_ds_bpermute((lane_now() ^ 32) << 2, __float_as_int(x)));
-}
 
 // ------------------------------------------------------------------ packing
 // fwdA[(tile*KQF + kq)*64 + lane] = float4 over kk = 4kq..4kq+3 of A[i=l&31][k=2kk+(l>>5)]
@@ -244,10 +239,6 @@ TOUED_DEV void store_gate_lds(const float* buf, __amdgpu_buffer_rsrc_t rs, long 
 //    part quad_vbyte, uniform part quad_soff.
 // Both keep a wave instruction's accesses in 512-byte or longer contiguous runs (HBM serves 128-byte row segments at
 // ~4.0 TB/s, contiguous KBs at ~5.9: tools/load_probe2.hip).
-// HIN_SLAB=0 (comparison builds): h_in in [256][M] rows (toued_gru_hin_slab() reports it to the host)
-#ifndef HIN_SLAB
-#define HIN_SLAB 1
-#endif
 TOUED_DEV unsigned slab_vbyte(int ub_, int col_) { return (unsigned)(ub_ * 128 + col_ * 4); }
 TOUED_DEV unsigned slab_soff(long c0, int h, int uq) { return (unsigned)(((c0 >> 5) + h) * 32768L + uq * 128); }
 TOUED_DEV unsigned quad_vbyte(int ub_, int col_) { return (unsigned)(((ub_ >> 2) * 32 + col_) * 16); }
@@ -465,7 +456,7 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define F6_SCALES ((F6_NFH + F6_NFA) * 256)   // float offset of the per-(gate, unit) weight scales 2^s [4][256]
 // f32 fragments of the augmented k-step (input weights and biases of r, z and the hn bias, scaled by 2^s):
 // [unit tile][gate r|z|hn][lane] float4 over kk = 0..3 of A[i = unit][k = 2 kk + (l >> 5)] (k < F: W_g[k][u],
-// k = 7: the bias), for the f32-MFMA input k-step (FWD_AUG32)
+// k = 7: the bias), for the f32-MFMA input k-step
 #define F6_A32 (F6_SCALES + 4 * HU)
 #define F6_FLOATS (F6_A32 + 8 * 3 * 64 * 4)   // packed size in floats (1 KiB fragment = 256 floats)
 #define F6_NGRP (16 * 8 * 3 + 8 * 4 + 8 * 3)  // k_pack_fwd6's fragment groups: h part, bf16 augmented, f32 augmented
@@ -558,7 +549,7 @@ __global__ void k_pack_fwd6(const float* __restrict__ eta, EtaOff o, int F, bf16
 #pragma unroll
     for (int q = 0; q < 2; ++q) out[(long)(grp * 2 + q) * 64 + lane] = __builtin_bit_cast(bf16x8, pc[q]);
   } else if (grp >= ngrp) {
-    // the f32 augmented fragments (FWD_AUG32)
+    // the f32 augmented fragments (the per-candidate instance)
     const int ga = grp - ngrp, g = ga % 3, ut = ga / 3;
     const int u = 32 * ut + (lane & 31);
     const float sg = scl[g * HU + u];
@@ -673,10 +664,6 @@ __device__ unsigned long long g_fwd_stamps[64 * 32 * 6];
     if (blockIdx.x < 64 && tid == 0 && s < 32)                                                         \
       g_fwd_stamps[(blockIdx.x * 32 + s) * 6 + (ph)] = __builtin_amdgcn_s_memtime();                   \
   } while (0)
-// the ping-pong schedule (FWD_PP): lane 0 of waves 0 and 4 record the start and end of each of their three pieces of
-// work per step (half 0: contraction k 0-7, k 8-15 + heads, gate maths; half 1: gate maths of the step before,
-// k 0-7, k 8-15), ordered clock reads
-__device__ unsigned long long g_fwd_pp[64 * 32 * 2 * 6];
 // the lockstep gate maths' inside (thread 0): after the done flags + gate_ain, after row tile 0, after row tile 1
 __device__ unsigned long long g_fwd_gm[64 * 32 * 4];
 #define GM_STAMP(k)                                                                                    \
@@ -688,55 +675,21 @@ TOUED_DEV unsigned long long fwd_clock() {
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c));
   return c;
 }
-#define PP_STAMP(s_, k)                                                                                \
-  do {                                                                                                 \
-    if (blockIdx.x < 64 && lane == 0 && (wave & 3) == 0 && (s_) >= 0 && (s_) < 32)                     \
-      g_fwd_pp[((blockIdx.x * 32 + (s_)) * 2 + grp) * 6 + (k)] = fwd_clock();                          \
-  } while (0)
 #else
 #define FWD_STAMP(ph) do {} while (0)
-#define PP_STAMP(s_, k) do {} while (0)
 #define GM_STAMP(k) do {} while (0)
 #endif
 
-#ifndef FWD_AUG32
-#define FWD_AUG32 1
-#endif
-#ifndef FWD_NOSAVE
-#define FWD_NOSAVE 0   // timing studies only: 1 = no saves, 2 = h_in only (the backward then reads stale data)
-#endif
-#ifndef FWD_HDEFER
-#define FWD_HDEFER 1   // the head reduce + softmax of step s at the end of step s + 1's contraction (wave 0)
-#endif
-#ifndef FWD_XFIRST
-#define FWD_XFIRST 0   // comparison runs: x(t) issued before the ring's lead fragments (the round-4 order)
-#endif
-#ifndef FWD_PP
-#define FWD_PP 0       // the two halves of the workgroup one interval apart (gate maths beside the partner's MFMAs)
-#endif
-#ifndef FWD_PP_PRIO
-#define FWD_PP_PRIO 0  // FWD_PP: the gate maths' issue priority over the partner wave's contraction
-#endif
-#ifndef FWD_XOR32
-#define FWD_XOR32 0    // the gate maths' head-partial fold through xor32 (no spilled lane index, no store drain)
-#endif
-#ifndef FWD_LANEB
-#define FWD_LANEB 0
-#endif
-#ifndef FWD_CAND0
-#define FWD_CAND0 0    // timing study only: the per-candidate instance reads candidate 0's fragments everywhere
-#endif
 template <bool SAVE>
 __global__ void __launch_bounds__(512, 1) k_gru_fwd6(FwdArgs p) {
-  constexpr bool A32 = FWD_AUG32 && !SAVE;   // the per-candidate (ES) instance: f32-MFMA augmented k-step
+  constexpr bool A32 = !SAVE;   // the per-candidate (ES) instance: f32-MFMA augmented k-step
   // carry image [row][unit]: slots 0, 1 the fp16 pieces of 2^14 h (MFMA B operand), slot 2 the bf16 residual
   __shared__ __attribute__((aligned(16))) __bf16 hB[3][64 * F6_HP];
   __shared__ __attribute__((aligned(16))) float wh[HU * 12];          // head weights [unit][pi | y0..y7 | pad]
   __shared__ __attribute__((aligned(16))) float usc[4 * HU];          // accumulator unscale 2^-(s + 14) [gate][unit]
-  // head partials [wave][output][row]; FWD_HDEFER: two buffers (step parity), reduced by wave 0 at the end of the next
-  // step's contraction, where it waits for the other waves' MFMAs anyway
-  __shared__ float hp[(FWD_HDEFER ? 2 : 1) * 8 * 9 * 64];
-  __shared__ float hout[FWD_HDEFER ? 1 : 9 * 64];
+  // head partials [wave][output][row] in two buffers (step parity): wave 0 reduces step s's at the end of step s + 1's
+  // contraction, where it waits for the other waves' MFMAs anyway
+  __shared__ float hp[2 * 8 * 9 * 64];
   __shared__ float wIs[8 * 4 * 64];     // gate_ain's W_in fragments [wave][kk][lane] (registers are the bound)
   __shared__ float hbias[9];            // pi_b, y_b[0..7] (the head reduce reads them from LDS)
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, col = lane & 31;
@@ -752,9 +705,7 @@ __global__ void __launch_bounds__(512, 1) k_gru_fwd6(FwdArgs p) {
   // per-candidate parameters in the ES inference mode (rows [c * rpc, (c + 1) * rpc) use candidate c)
   const int cand = SAVE ? 0 : r0 / p.rpc;
   const float* eta = p.eta + (long)cand * p.eta_stride;
-  // FWD_CAND0 (timing study only, wrong results): every workgroup streams candidate 0's packed fragments, which then
-  // stay L2-resident -- the per-candidate fragment stream's cost is the difference to the production kernel
-  const float* A6c = reinterpret_cast<const float*>(p.A6) + (long)(FWD_CAND0 ? 0 : cand) * p.a_stride4 * 4;
+  const float* A6c = reinterpret_cast<const float*>(p.A6) + (long)cand * p.a_stride4 * 4;
   for (int i = tid; i < HU * 12; i += 512) {
     const int u = i / 12, oo = i - u * 12;
     wh[i] = oo == 0 ? eta[p.o.pi_w + u] : oo < 9 ? eta[p.o.y_w + u * 8 + (oo - 1)] : 0.0f;
@@ -794,8 +745,8 @@ __global__ void __launch_bounds__(512, 1) k_gru_fwd6(FwdArgs p) {
   // half a step late so the two halves contract at different times (later rounds inherit the offset)
   if (p.stagger > 0 && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1))
     for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  // FWD_HDEFER: step s_'s heads from its partials (wave 0, lane = row): the bias plus the eight waves' partials in
-  // wave order, then pi_hat and the softmax of the eight y logits -- the arithmetic of the reduce below, in one lane
+  // step s_'s heads from its partials (wave 0, lane = row): the bias plus the eight waves' partials in wave order,
+  // then pi_hat and the softmax of the eight y logits
   auto head_out = [&](int s_) {
     const int tl = lane_now(), t_ = T - 1 - s_;
     const float* hb = hp + (s_ & 1) * 4608;
@@ -814,288 +765,6 @@ __global__ void __launch_bounds__(512, 1) k_gru_fwd6(FwdArgs p) {
     const float inv = 1.0f / ssum;
     for (int j = 0; j < 8; ++j) p.y_hat[((long)t_ * 8 + j) * R + r0 + tl] = e[j] * inv;
   };
-if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one spills with it)
-  // ---- ping-pong schedule: the workgroup's two halves (waves 0-3 own units 0-127 = k-steps 0-7 of the carry, waves
-  // 4-7 units 128-255 = k-steps 8-15) run one interval apart, three intervals per step with a barrier after each:
-  //   interval   waves 0-3 (half 0)                          waves 4-7 (half 1)
-  //   1          contraction k 0-7 of step s (own units)     gate maths of step s-1: writes units 128-255
-  //   2          contraction k 8-15 + augmented of step s    contraction k 0-7 of step s
-  //   3          gate maths of step s: writes units 0-127    contraction k 8-15 + augmented of step s
-  // so each SIMD (waves w and w + 4) has one wave's gate maths (VALU, saves) beside its partner's matrix work in two
-  // of the three intervals, where the lockstep order runs them one after the other.  Every interval reads carry units
-  // that no wave writes in it (the table above), so the carry stays single-buffered in place; the k-order of the
-  // contraction is unchanged.  Heads: step s's partials (both halves) are complete after interval 1 of step s + 1;
-  // wave 0 reduces them in its interval 2 (FWD_HDEFER's double buffer).
-  static_assert(FWD_HDEFER, "FWD_PP defers the heads");
-  const int grp = wave >> 2;
-  floatx16 acc[3][2];   // r, z, W_hn h + b_hn (the n gate's input part is gate_ain, on the VALU)
-  float xv[2][7];
-  f16x8 A0[3][2], A1[3][2], B[2][2];
-  auto fragA = [&](int ks, int g, int q) { return ((ks * 8 + wave) * 3 + g) * 2 + q; };
-  auto fragAug = [&](int g, int q) { return F6_NFH + (wave * 4 + g) * 3 + q; };
-  auto load_B = [&](int ks, int h) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      B[h][q] = *reinterpret_cast<const f16x8*>(&hB[q][(RB * h + col) * F6_HP + 16 * ks + 8 * hi]);
-  };
-  // one k-step: refill its A ring slot two k-steps ahead (reload), load the next k-step's B fragments (nextB)
-  auto kstep = [&](int ks, f16x8 (&Ar)[3][2], bool reload, bool nextB) {
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        acc[g][h] = mfma3h(Ar[g], B[h], acc[g][h]);
-        if (g == 2 && nextB) load_B(ks + 1, h);
-      }
-      if (reload) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) Ar[g][q] = ldAh(fragA(ks + 2, g, q));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // the contraction's first half: x(t), the ring's lead fragments, k-steps 0-7 (carry units 0-127)
-  auto c_first = [&](int s) {
-    const int t = T - 1 - s;
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[g][h][q] = 0.0f;
-      {
-        auto ring = [&] {
-  #pragma unroll
-          for (int g = 0; g < 3; ++g)
-  #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              A0[g][q] = ldAh(fragA(0, g, q));
-              A1[g][q] = ldAh(fragA(1, g, q));
-            }
-        };
-        if (!FWD_XFIRST) ring();
-  #pragma unroll
-        for (int h = 0; h < 2; ++h)
-  #pragma unroll
-          for (int f = 0; f < 7; ++f) {
-            const int fc = f < F ? f : F - 1;
-            xv[h][f] = ld_u(rs_X, (unsigned)((RB * h + col) * p.xs_col * 4),
-                            (unsigned)((fc * p.xs_f + ((long)t * R + r0) * p.xs_col) * 4));
-          }
-        if (FWD_XFIRST) ring();
-      }
-    load_B(0, 0);
-    load_B(0, 1);
-#pragma nounroll
-    for (int kp = 0; kp < 3; ++kp) {
-      kstep(2 * kp, A0, true, true);
-      kstep(2 * kp + 1, A1, true, true);
-    }
-    kstep(6, A0, true, true);
-    kstep(7, A1, true, false);   // (k-step 8's B: units 128-143, written by the other half in this interval)
-  };
-  // the second half: k-steps 8-15 (carry units 128-255) and the augmented k-step
-  auto c_second = [&](int s) {
-    load_B(8, 0);
-    load_B(8, 1);
-#pragma nounroll
-    for (int kp = 4; kp < 7; ++kp) {
-      kstep(2 * kp, A0, true, true);
-      kstep(2 * kp + 1, A1, true, true);
-    }
-    kstep(14, A0, false, true);
-      f16x8 (&A)[3][2] = A1;   // k-step 15
-      if (A32) {
-        // the augmented k-step on the f32 MFMA (exact products): A = the scaled input weights and biases (one 16-byte
-        // fragment per gate, 3 KB per wave-step instead of the bf16 triple's 12 KB: the ES candidates' per-step stream
-        // from the Infinity Cache is what this kernel waits on), B = 2^14 [x_k (k < F), 1 (k = 7)]
-        float4 a32[3];
-  #pragma unroll
-        for (int g = 0; g < 3; ++g)
-          a32[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                  rs_A, (int)vA, (F6_A32 + (wave * 3 + g) * 256) * 4, 0));
-  #pragma unroll
-        for (int g = 0; g < 3; ++g) {
-  #pragma unroll
-          for (int h = 0; h < 2; ++h) acc[g][h] = mfma3h(A[g], B[h], acc[g][h]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-  #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const int k = 2 * kk + hi;
-          float bx[2];
-  #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            // static indices: the lane's k = 2 kk + hi picks between two registers (a lane-dependent index puts xv in
-            // scratch: 64 bytes per lane, C4's forward 2.22 -> 2.65 ms while xv lived outside the step loop)
-            const float xs = hi ? xv[h][2 * kk + 1 < 7 ? 2 * kk + 1 : 6] : xv[h][2 * kk];
-            bx[h] = (k < F ? xs : (k == 7 ? 1.0f : 0.0f)) * HSCALE;
-          }
-  #pragma unroll
-          for (int g = 0; g < 3; ++g) {
-            const float av = kk == 0 ? a32[g].x : kk == 1 ? a32[g].y : kk == 2 ? a32[g].z : a32[g].w;
-  #pragma unroll
-            for (int h = 0; h < 2; ++h) acc[g][h] = mfma32(av, bx[h], acc[g][h]);
-          }
-        }
-      } else {
-      // last carry k-step; each gate's augmented fragments (three bf16 pieces) load behind its MFMAs
-      bf16x8 Aa[3][3], Ba[2][3];
-  #pragma unroll
-      for (int g = 0; g < 3; ++g) {
-  #pragma unroll
-        for (int h = 0; h < 2; ++h) acc[g][h] = mfma3h(A[g], B[h], acc[g][h]);
-  #pragma unroll
-        for (int q = 0; q < 3; ++q) Aa[g][q] = ldA(fragAug(g, q));
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // augmented k-step: B = bf16 pieces of 2^14 [x, 1, 0 ...]
-  #pragma unroll
-      for (int h = 0; h < 2; ++h)
-  #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float v = hi ? 0.0f : e < F ? xv[h][e < 7 ? e : 6] : (e == F ? 1.0f : 0.0f);
-          split3v(v * HSCALE, Ba[h][0], Ba[h][1], Ba[h][2], e);
-        }
-  #pragma unroll
-      for (int g = 0; g < 3; ++g) {
-  #pragma unroll
-        for (int h = 0; h < 2; ++h) acc[g][h] = mfma6(Aa[g], Ba[h], acc[g][h]);
-      }
-      }
-  };
-  auto g_maths = [&](int s) {
-    const int t = T - 1 - s;
-    // (FWD_PP_PRIO: the gate maths' VALU ahead of the partner's MFMA issue on the SIMD)
-    if (FWD_PP_PRIO) __builtin_amdgcn_s_setprio(FWD_PP_PRIO);
-      // ---- gate maths (lane = row 32h + col, register q = unit 32 wave + 4 hi + qunit(q))
-      floatx16 ain[2];
-      // done flags d_{t-1} of the lane's two rows, issued before the saves so their wait drains nothing else
-      // (lane offset re-derived here: a spilled copy's reload would wait on every outstanding access)
-      bool dnf[2];
-  #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        dnf[h] = (t >= 1) ? __builtin_amdgcn_raw_buffer_load_b8(
-                                rs_done, lane_now() & 31, (int)(((long)a_[h] * T + (t - 1)) * W + r0 + RB * h - a_[h] * W),
-                                0) != 0
-                          : false;
-      float wI[4];
-      {
-        const int ln = lane_now();
-  #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) wI[kk] = wIs[(wave * 4 + kk) * 64 + ln];
-      }
-  #pragma unroll
-      for (int h = 0; h < 2; ++h) ain[h] = gate_ain(wI, F, hi, [&](int k) { return xv[h][k < 7 ? k : 6]; });
-      const long cbase = (long)t * R;
-      const int ub = 32 * wave + 4 * hi;
-      const float4* whl = reinterpret_cast<const float4*>(wh + ub * 12);
-  #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int row = RB * h + col;
-        const bool dn = dnf[h];
-        const unsigned vq = quad_vbyte(ub, col), vslab = slab_vbyte(ub, col);
-        float hp_loc[9];
-  #pragma unroll
-        for (int oo = 0; oo < 9; ++oo) hp_loc[oo] = 0.0f;
-  #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          // four consecutive units ub + 8 g4 .. +3 of this row: h_in pieces, then the new carry's pieces
-          const int ho = row * F6_HP + ub + 8 * g4;
-          const f16x4 h0 = *reinterpret_cast<const f16x4*>(&hB[0][ho]);
-          const f16x4 h1 = *reinterpret_cast<const f16x4*>(&hB[1][ho]);
-          const bf16x4 hr = *reinterpret_cast<const bf16x4*>(&hB[2][ho]);
-          // the saves of this register quad: h_in (rebuilt exactly from its pieces) per unit in its slab blocks; r, z,
-          // hn one 16-byte store each in their unit-quad blocks (quad_soff) after the gate maths
-          const unsigned sq = quad_soff(cbase + r0, h, g4);
-          float sv[3][4];
-          float us[3][4];
-  #pragma unroll
-          for (int g = 0; g < 3; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(&usc[g * HU + ub + 8 * g4]);
-            us[g][0] = v.x; us[g][1] = v.y; us[g][2] = v.z; us[g][3] = v.w;
-          }
-          f16x4 n0, n1;
-          bf16x4 nr;
-  #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int q = 4 * g4 + e;
-            const float rg = sigm_r(acc[0][h][q] * us[0][e]);
-            const float zg = sigm_r(acc[1][h][q] * us[1][e]);
-            const float hn = acc[2][h][q] * us[2][e];
-            const float ng = gate_n(ain[h][q], rg, hn);
-            const float hin = (((float)h0[e] + (float)h1[e]) + (float)hr[e]) * (1.0f / HSCALE);   // exact
-            const float hh = (1.0f - zg) * ng + zg * hin;
-            split_carry(dn ? 0.0f : hh, n0, n1, nr, e);   // carry h_in(t-1) = where(d_{t-1}, 0, h_out(t))
-            sv[0][e] = rg;
-            sv[1][e] = zg;
-            sv[2][e] = hn;   // n is recomputed by the backward (gate_n)
-            if (SAVE && FWD_NOSAVE != 1) {   // (FWD_NOSAVE, timing studies only: 1 = no saves, 2 = h_in only)
-              if (HIN_SLAB) st_u(rs_hin, vslab, slab_soff(cbase + r0, h, qunit(q)), hin);
-              else st_u(rs_hin, (unsigned)(((long)ub * p.M + r0 + row) * 4), (unsigned)(((long)qunit(q) * p.M + cbase) * 4), hin);
-            }
-            const float rl = fmaxf(hh, 0.0f);
-            const float4 w0 = whl[qunit(q) * 3], w1 = whl[qunit(q) * 3 + 1], w2 = whl[qunit(q) * 3 + 2];
-            hp_loc[0] += rl * w0.x; hp_loc[1] += rl * w0.y; hp_loc[2] += rl * w0.z;
-            hp_loc[3] += rl * w0.w; hp_loc[4] += rl * w1.x; hp_loc[5] += rl * w1.y;
-            hp_loc[6] += rl * w1.z; hp_loc[7] += rl * w1.w; hp_loc[8] += rl * w2.x;
-          }
-          if (SAVE && FWD_NOSAVE == 0) {   // (FWD_NOSAVE, timing studies only: 1 = no saves, 2 = h_in only)
-            st4(rs_r, vq, sq, sv[0]);
-            st4(rs_z, vq, sq, sv[1]);
-            st4(rs_hn, vq, sq, sv[2]);
-          }
-          *reinterpret_cast<f16x4*>(&hB[0][ho]) = n0;
-          *reinterpret_cast<f16x4*>(&hB[1][ho]) = n1;
-          *reinterpret_cast<bf16x4*>(&hB[2][ho]) = nr;
-        }
-        // lanes l and l + 32 hold the same row: fold the two halves, one lane writes
-  #pragma unroll
-        for (int oo = 0; oo < 9; ++oo) {
-          const float o = __shfl_xor(hp_loc[oo], 32);
-          if (hi == 0) hp[(FWD_HDEFER ? (s & 1) * 4608 : 0) + (wave * 9 + oo) * 64 + row] = hp_loc[oo] + o;
-        }
-      }
-    if (FWD_PP_PRIO) __builtin_amdgcn_s_setprio(0);
-  };
-  // (each half's three roles in program order, so the ring and B registers are dead across the gate maths)
-  if (grp == 0) {
-    for (int s = 0; s < T; ++s) {
-      PP_STAMP(s, 0);
-      c_first(s);
-      PP_STAMP(s, 1);
-      lds_barrier();
-      PP_STAMP(s, 2);
-      c_second(s);
-      if (wave == 0 && s > 0) head_out(s - 1);
-      PP_STAMP(s, 3);
-      lds_barrier();
-      PP_STAMP(s, 4);
-      g_maths(s);
-      PP_STAMP(s, 5);
-      lds_barrier();
-    }
-    lds_barrier();   // (the other half's last gate maths)
-    if (wave == 0) head_out(T - 1);
-  } else {
-    for (int s = 0; s < T; ++s) {
-      PP_STAMP(s, 0);
-      if (s > 0) g_maths(s - 1);
-      PP_STAMP(s, 1);
-      lds_barrier();
-      PP_STAMP(s, 2);
-      c_first(s);
-      PP_STAMP(s, 3);
-      lds_barrier();
-      PP_STAMP(s, 4);
-      c_second(s);
-      PP_STAMP(s, 5);
-      lds_barrier();
-    }
-    g_maths(T - 1);
-    lds_barrier();
-  }
-} else {
   for (int s = 0; s < T; ++s) {
     const int t = T - 1 - s;
     FWD_STAMP(0);
@@ -1113,15 +782,15 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
     // at the end of the contraction (lanes 32-63 hold k = 8..15: zero); A fragments through a two-k-step ring (A0: even
     // k-steps, A1: odd): each L2 fragment load has a whole k-step of the wave's MFMAs (plus the partner wave's) to land
     // instead of one gate's.  (Declared in the step: hoisted out of the loop, the C4 per-candidate instance ran 2.61-2.69
-    // instead of 2.22 ms.)  The ring's first two k-steps go out ahead of x (FWD_XFIRST=0: the first ring wait does not
-    // wait for x's HBM loads; 1.207-1.216 ms either order at C2)
+    // instead of 2.22 ms.)  The ring's first two k-steps go out ahead of x: the first ring wait does not wait for x's
+    // HBM loads (1.207-1.216 ms either order at C2)
     float xv[2][7];
     f16x8 A0[3][2], A1[3][2], B[2][2];
 
     auto fragA = [&](int ks, int g, int q) { return ((ks * 8 + wave) * 3 + g) * 2 + q; };
     auto fragAug = [&](int g, int q) { return F6_NFH + (wave * 4 + g) * 3 + q; };
     {
-      auto ring = [&] {
+      auto ring = [&] {   // (a lambda: written inline, both instances' register allocation changes)
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -1130,7 +799,7 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
             A1[g][q] = ldAh(fragA(1, g, q));
           }
       };
-      if (!FWD_XFIRST) ring();
+      ring();
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -1139,13 +808,9 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
           xv[h][f] = ld_u(rs_X, (unsigned)((RB * h + col) * p.xs_col * 4),
                           (unsigned)((fc * p.xs_f + ((long)t * R + r0) * p.xs_col) * 4));
         }
-      if (FWD_XFIRST) ring();
     }
     auto load_B = [&](int ks, int h) {
-      // (FWD_LANEB: the lane's row and half re-derived instead of a register kept across the step loop -- no spill,
-      // but the contraction issued slower: 1.150-1.152 vs 1.131-1.136 ms, r06t34)
-      const int ln = FWD_LANEB ? lane_now() : lane;
-      const int cl = ln & 31, hl = ln >> 5;
+      const int cl = lane & 31, hl = lane >> 5;
 #pragma unroll
       for (int q = 0; q < 2; ++q)
         B[h][q] = *reinterpret_cast<const f16x8*>(&hB[q][(RB * h + cl) * F6_HP + 16 * ks + 8 * hl]);
@@ -1233,7 +898,7 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
       for (int h = 0; h < 2; ++h) acc[g][h] = mfma6(Aa[g], Ba[h], acc[g][h]);
     }
     }
-    if (FWD_HDEFER && s > 0 && wave == 0) head_out(s - 1);   // (wave 0 leads its SIMD: it waits here anyway)
+    if (s > 0 && wave == 0) head_out(s - 1);   // (wave 0 leads its SIMD: it waits here anyway)
     FWD_STAMP(1);
     lds_barrier();   // every wave done reading hB / xB: the carry and x(t-1) overwrite them in place
     FWD_STAMP(2);
@@ -1300,17 +965,14 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
           sv[0][e] = rg;
           sv[1][e] = zg;
           sv[2][e] = hn;   // n is recomputed by the backward (gate_n)
-          if (SAVE && FWD_NOSAVE != 1) {   // (FWD_NOSAVE, timing studies only: 1 = no saves, 2 = h_in only)
-            if (HIN_SLAB) st_u(rs_hin, vslab, slab_soff(cbase + r0, h, qunit(q)), hin);
-            else st_u(rs_hin, (unsigned)(((long)ub * p.M + r0 + row) * 4), (unsigned)(((long)qunit(q) * p.M + cbase) * 4), hin);
-          }
+          if (SAVE) st_u(rs_hin, vslab, slab_soff(cbase + r0, h, qunit(q)), hin);
           const float rl = fmaxf(hh, 0.0f);
           const float4 w0 = whl[qunit(q) * 3], w1 = whl[qunit(q) * 3 + 1], w2 = whl[qunit(q) * 3 + 2];
           hp_loc[0] += rl * w0.x; hp_loc[1] += rl * w0.y; hp_loc[2] += rl * w0.z;
           hp_loc[3] += rl * w0.w; hp_loc[4] += rl * w1.x; hp_loc[5] += rl * w1.y;
           hp_loc[6] += rl * w1.z; hp_loc[7] += rl * w1.w; hp_loc[8] += rl * w2.x;
         }
-        if (SAVE && FWD_NOSAVE == 0) {   // (FWD_NOSAVE, timing studies only: 1 = no saves, 2 = h_in only)
+        if (SAVE) {
           st4(rs_r, vq, sq, sv[0]);
           st4(rs_z, vq, sq, sv[1]);
           st4(rs_hn, vq, sq, sv[2]);
@@ -1322,42 +984,17 @@ if constexpr (FWD_PP && SAVE) {   // (C2 instance only: the per-candidate one sp
       // lanes l and l + 32 hold the same row: fold the two halves, one lane writes
 #pragma unroll
       for (int oo = 0; oo < 9; ++oo) {
-        const float o = FWD_XOR32 ? xor32(hp_loc[oo]) : __shfl_xor(hp_loc[oo], 32);
-        const int rw = FWD_XOR32 ? RB * h + (lane_now() & 31) : row;   // (re-derived: no spilled address either)
-        if (hi == 0) hp[(FWD_HDEFER ? (s & 1) * 4608 : 0) + (wave * 9 + oo) * 64 + rw] = hp_loc[oo] + o;
+        const float o = __shfl_xor(hp_loc[oo], 32);
+        if (hi == 0) hp[(s & 1) * 4608 + (wave * 9 + oo) * 64 + row] = hp_loc[oo] + o;
       }
       GM_STAMP(1 + h);
     }
     FWD_STAMP(3);
     lds_barrier();   // head partials, the carry and x(t-1) visible
     FWD_STAMP(4);
-    if (FWD_HDEFER) {
-      FWD_STAMP(5);
-      continue;
-    }
-    for (int i = 64 * wave + lane_now(); i < 9 * 64; i += 512) {
-      const int oo = i >> 6, c = i & 63;
-      float v = hbias[oo];
-#pragma unroll
-      for (int gq = 0; gq < 8; ++gq) v += hp[(gq * 9 + oo) * 64 + c];
-      hout[i] = v;
-    }
-    lds_barrier();
-    if (tid < 64) {
-      const int tl = lane_now();   // == tid (wave 0)
-      const long ob = (long)t * R + r0 + tl;
-      p.pi_hat[ob] = hout[tl];
-      float m = -__builtin_inff();
-      for (int j = 0; j < 8; ++j) m = fmaxf(m, hout[(j + 1) * 64 + tl]);
-      float e[8], ssum = 0.0f;
-      for (int j = 0; j < 8; ++j) { e[j] = __expf(hout[(j + 1) * 64 + tl] - m); ssum += e[j]; }
-      const float inv = 1.0f / ssum;
-      for (int j = 0; j < 8; ++j) p.y_hat[((long)t * 8 + j) * R + r0 + tl] = e[j] * inv;
-    }
     FWD_STAMP(5);
   }
-  if (FWD_HDEFER && wave == 0) head_out(T - 1);   // the last step's heads (its partials visible: the loop's barrier)
-}
+  if (wave == 0) head_out(T - 1);   // the last step's heads (its partials visible: the loop's barrier)
 }
 
 // ------------------------------------------------------------------ backward
@@ -1619,19 +1256,10 @@ __device__ int g_bwd_wsimd[64 * 8];
 //   SMALL (F <= 6): the two small weight-gradient products GI = [X; 1] . dn^T and DH . relu(h_out)^T accumulate in
 //     the kernel (16x16x4 f32 MFMA, exact f32 products) instead of streaming dn and relu(h_out) to HBM for a later
 //     reduction: see small_mfma below.
-#ifndef BWD_MPRIO
-#define BWD_MPRIO 0
-#endif
-// BWD_TRECOMP (timing study only, wrong results): the gate pre-activations W_hr h, W_hz h and
-// W_hn h recomputed on the matrix pipe at the top of every step (the forward's 16 carry k-steps: 3 gates x 2 row tiles
-// x scaled fp16 pairs, A fragments through a two-k-step L2 ring, B from the image) and the memory part loading only
-// h_in: a lower bound on the step of a recompute backward (no h_in image build, no augmented input k-step)
-#ifndef BWD_TRECOMP
-#define BWD_TRECOMP 0
-#endif
 // BWD_PK: the memory part's per-element gate maths on element pairs (packed FP32: v_pk_{add,mul,fma}_f32, two
 // elements per instruction; 350 fewer VALU instructions in the kernel, k_gru_bwd6n 7.42 -> 7.27-7.34 ms, round 6
-// profiles/r06/r06t12_ab.log; the same head-partial pairing in the forward measured no gain and was dropped)
+// profiles/r06/r06t12_ab.log; the same head-partial pairing in the forward measured no gain and was dropped).  The
+// scalar form stays as the 0 setting: without it the kernel loses the lane_now() of its `wil`, and so changes
 #ifndef BWD_PK
 #define BWD_PK 1
 #endif
@@ -1789,14 +1417,6 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #ifndef BWD_RD
 #define BWD_RD 4
 #endif
-#ifndef BWD_SPREAD
-#define BWD_SPREAD 0
-#endif
-  // BWD_SPREAD: the pass's 32 DG stores per lane (one gate's cotangent of both row tiles, held in registers) go two per
-  // k-step between the MFMAs, where the vector memory pipe carries only the A ring, instead of as a burst in front of
-  // the pass (the store path takes ~11 B/clk per CU: a 64 KB burst per CU held the waves ~5.7 k cycles per gate).
-  // Slot s = 2 RD gi + i of ring group gi (i static): row tile h = s >> 4, register q = s & 15; the queue qv is rotated
-  // by 2 RD after each rolled group so that its indices stay static.
   // SMALL (the fused path, read only by toued_wgrad_bfp_slab): each gate's cotangent DG_g in 32-column slab blocks,
   // [M / 32][256][32] (element (u, c) at ((c >> 5) * 256 + u) * 32 + (c & 31)): a reduction workgroup's B slab (256
   // rows x 32 columns) is then 32 KB of contiguous HBM instead of 256 rows x 128 bytes 4 M bytes apart, which HBM
@@ -1809,39 +1429,15 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     return SMALL ? (unsigned)((((ctr_ + r0) >> 5) + h) * 32768L + uq * 128)
                  : (unsigned)((((long)uq * p.M + ctr_) * 4) + 128 * h);
   };
-  auto store_slot = [&](int gst, long ctr_, int gi, int i, float v) {
-    const int s_ = 2 * BWD_RD * gi + i, h = s_ >> 4, e = s_ & 3, g4 = (s_ & 15) >> 2;
-    const int ln = lane_now();
-    st_u(rs_dg[gst], dg_vbyte(32 * wave + 4 * (ln >> 5), ln & 31), dg_soff(ctr_, e + 8 * g4, h), v);
-  };
-  // pre: called once in the pass after its last ring reload (k-step 16 - RD): loads issued there stay outstanding
-  // behind every ring wait of the pass (vmcnt counts in issue order), so they cost the pass nothing
-  // BWD_SPLACE: where the DG stores go.  vmcnt counts loads and stores in issue order, so a ring load issued behind a
-  // 64 KB store burst is waited for only once the burst has drained (HBM-write-bound when every CU stores at once):
-  // with the stores right in front of a pass, its first MFMAs waited for them.  Here each pass's first RD ring slots
-  // are loaded ahead of the stores -- in the previous pass's last RD k-steps, into the slots those k-steps free (no
-  // extra registers), or before the dr split's stores -- and the dz / dhn stores go out at the end of the previous
-  // pass (dz_r, dhn_r are live there anyway), so a burst drains during the barrier, the refill and RD k-steps.
-#ifndef BWD_SPLACE
-#define BWD_SPLACE 0
-#endif
-  static_assert(!BWD_SPLACE || (!BWD_SPREAD && 16 % BWD_RD == 0), "BWD_SPLACE: burst stores, RD dividing 16");
-  f16x8 ring[BWD_RD][2];
-  auto preload_ring = [&](int g) {
+  // one gate pass over the image
+  auto contract_h = [&](int g) {
+    constexpr int RD = BWD_RD;                    // A-fragment ring depth (k-steps in flight from L2)
+    f16x8 ring[RD][2], B[2][2];
+    int sb = 0, sb1 = 1;   // the image slots of the two fp16 pieces (plain ints: see tools/device_asm_diff.py)
 #pragma unroll
-    for (int i = 0; i < BWD_RD; ++i)
+    for (int i = 0; i < RD; ++i)
 #pragma unroll
       for (int q = 0; q < 2; ++q) ring[i][q] = ldAh(i, g, q);
-  };
-  // nextg >= 0 (BWD_SPLACE): the last RD k-steps load pass nextg's first RD slots; post() runs after the last k-step
-  // inpass(j): called after each of the last four k-steps (j = 0..3, the unrolled tail without ring reloads), where the
-  // matrix pipe paces the wave and VALU / LDS work rides beside it (BWD_INPASS: the next gate's first piece)
-  auto contract_h = [&](int g, int sb, int sb1, float (&qv)[32], long ctr_, auto&& pre, bool preloaded, int nextg,
-                        auto&& post, auto&& inpass) {   // sb, sb1: the image slots of the two fp16 pieces
-    constexpr int RD = BWD_RD;                    // A-fragment ring depth (k-steps in flight from L2)
-    static_assert(!BWD_SPREAD || 16 % RD == 0, "the spread stores: 2 per k-step, 2 RD per ring group");
-    f16x8 B[2][2];
-    if (!preloaded) preload_ring(g);
     const int ln = lane_now(), bl = (ln & 31) * PP + 8 * (ln >> 5);
     auto ldB = [&](int ks, int h) {
 #pragma unroll
@@ -1849,15 +1445,11 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     };
     ldB(0, 0);
     ldB(0, 1);
-    auto kstep = [&](int ks, f16x8 (&Ar)[2], bool reload, int gi, int j) {
+    auto kstep = [&](int ks, f16x8 (&Ar)[2], bool reload) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         acc[h] = mfma3h(Ar, B[h], acc[h]);
         if (ks + 1 < 16) ldB(ks + 1, h);
-        if (BWD_SPREAD && h == 0) {
-          store_slot(g, ctr_, gi, 2 * j, qv[2 * j]);
-          store_slot(g, ctr_, gi, 2 * j + 1, qv[2 * j + 1]);
-        }
       }
       if (reload) {
 #pragma unroll
@@ -1870,58 +1462,24 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #pragma nounroll
     for (int gi = 0; gi < NG; ++gi) {
 #pragma unroll
-      for (int j = 0; j < RD; ++j) kstep(gi * RD + j, ring[j], true, gi, j);
-      if (BWD_SPREAD) {
-#pragma unroll
-        for (int i = 0; i < 32 - 2 * RD; ++i) qv[i] = qv[i + 2 * RD];
-      }
+      for (int j = 0; j < RD; ++j) kstep(gi * RD + j, ring[j], true);
     }
 #pragma unroll
     for (int ks = NG * RD; ks < 16; ++ks) {
-      kstep(ks, ring[ks % RD], ks + RD < 16, NG, ks - NG * RD);
-      if (ks == 16 - RD) {   // (16 - RD >= NG RD: always in the unrolled tail)
-        pre();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (BWD_SPLACE && nextg >= 0 && ks >= 16 - RD) {   // this k-step's slot is free: pass nextg's slot ks - (16 - RD)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) ring[ks % RD][q] = ldAh(ks - (16 - RD), nextg, q);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (ks >= 12) {
-        inpass(ks - 12);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      kstep(ks, ring[ks % RD], ks + RD < 16);
+      // (further scheduling barriers after the last ring reload and after each of the last four k-steps: they move no
+      // instruction but print in the assembly, which tools/device_asm_diff.py compares as text)
+      if (ks == 16 - RD) __builtin_amdgcn_sched_barrier(0);
+      if (ks >= 12) __builtin_amdgcn_sched_barrier(0);
     }
-    post();
   };
   // scaled fp16 pieces of the four units u0 .. u0 + 3 of row `row` into image slots 0, 1
-#ifndef BWD_INPASS
-#define BWD_INPASS 0
-#endif
-#ifndef BWD_TREFILL
-#define BWD_TREFILL 0   // timing studies only (wrong results): 1 = refills without LDS writes, 2 = without the split
-#endif
   auto put4h = [&](int row, int u0, const float (&v)[4], float sc) {
-    f16x4 x0, x1;
-    if (BWD_TREFILL == 2) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { x0[e] = (_Float16)0.0f; x1[e] = (_Float16)0.0f; }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) split2h(v[e] * sc, x0, x1, e);
-    }
-    if (BWD_TREFILL != 1) {
-      *reinterpret_cast<f16x4*>(&dgB[0][row * PP + u0]) = x0;
-      *reinterpret_cast<f16x4*>(&dgB[1][row * PP + u0]) = x1;
-    }
-  };
-  // BWD_INPASS: one of the two pieces (which) into image slot `slot`
-  auto put1h = [&](int slot, int which, int row, int u0, const float (&v)[4], float sc) {
     f16x4 x0, x1;
 #pragma unroll
     for (int e = 0; e < 4; ++e) split2h(v[e] * sc, x0, x1, e);
-    *reinterpret_cast<f16x4*>(&dgB[slot][row * PP + u0]) = which ? x1 : x0;
+    *reinterpret_cast<f16x4*>(&dgB[0][row * PP + u0]) = x0;
+    *reinterpret_cast<f16x4*>(&dgB[1][row * PP + u0]) = x1;
   };
   // SMALL: the wave's dn and relu(h_out) of one row tile and one 16-unit half go through a wave-private [row][unit]
   // f32 block in image slot 0 (free during the memory part) as the B operand B[k][j = unit] of 16x16x4 f32 MFMAs over
@@ -1960,14 +1518,10 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     // 8 g4 per lane (eight consecutive units x 32 rows, 1 KB contiguous per wave instruction), lane-quad transposed
     // in the memory part
     const unsigned vq = quad_vbyte(ub, col), sq = quad_soff(ctr_ + r0, h, g4);
-    if (HIN_SLAB) ld4(rs_hin, slab_vbyte(ub + (col & 3), col & 28), slab_soff(ctr_ + r0, h, 8 * g4), v[0]);
-    else ld4(rs_hin, (unsigned)((((long)(ub + (col & 3))) * p.M + r0 + RB * h + (col & 28)) * 4),
-             (unsigned)(((long)8 * g4 * p.M + ctr_) * 4), v[0]);
-    if (!BWD_TRECOMP) {
-      ld4(rs_r, vq, sq, v[1]);
-      ld4(rs_z, vq, sq, v[2]);
-      ld4(rs_hn, vq, sq, v[3]);
-    }
+    ld4(rs_hin, slab_vbyte(ub + (col & 3), col & 28), slab_soff(ctr_ + r0, h, 8 * g4), v[0]);
+    ld4(rs_r, vq, sq, v[1]);
+    ld4(rs_z, vq, sq, v[2]);
+    ld4(rs_hn, vq, sq, v[3]);
   };
   // the rows' inputs x(t) as gate_ain's B fragments (lane = row RB h + col, k = 2 kk + hi): n is recomputed.
   // Tile 0's go out with the first quads, tile 1's beside the ring loads of quad 3.
@@ -1980,21 +1534,11 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
       x[kk] = ld_u(rs_x, (unsigned)((((long)(k < F ? k : 0)) * p.M + RB * h + (ln & 31)) * 4), (unsigned)((ctr_ + r0) * 4));
     }
   };
-  // the first NR - 1 quads and tile 0's x of step t: quads [0, BWD_PF) (and x when BWD_PFX) in the previous step's dhn
-  // pass after its last ring reload, so that they land during that pass, the tail and the head; the rest at the top of
-  // the step's memory part
-#ifndef BWD_PF
-#define BWD_PF 0
-#endif
-#ifndef BWD_PFX
-#define BWD_PFX 0
-#endif
-  static_assert(BWD_PF >= 0 && BWD_PF <= NR - 1, "BWD_PF: at most the ring's NR - 1 leading quads");
-  auto load_first = [&](long ctr_, bool pre) {
-    if (pre == (bool)BWD_PFX) load_x(ctr_, 0, xa);
+  // the first NR - 1 quads and tile 0's x of step t, at the top of the step's memory part
+  auto load_first = [&](long ctr_) {
+    load_x(ctr_, 0, xa);
 #pragma unroll
-    for (int qi = 0; qi < NR - 1; ++qi)
-      if (pre == (qi < BWD_PF)) load_q(ctr_, qi >> 2, qi & 3, vr[qi]);
+    for (int qi = 0; qi < NR - 1; ++qi) load_q(ctr_, qi >> 2, qi & 3, vr[qi]);
   };
   // TOUED_BWD_STAGGER (study): first-round workgroups start late by phase * stagger quanta (~8 k cycles each), phase
   // by mode: 0 = alternate CUs of every XCD, 1 = alternate XCDs, 2 = four phases over the CUs of every XCD
@@ -2002,61 +1546,14 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     const int ph = p.stagger_mode == 0 ? (blockIdx.x >> 3) & 1 : p.stagger_mode == 1 ? blockIdx.x & 1 : (blockIdx.x >> 3) & 3;
     for (int i = 0; i < ph * p.stagger; ++i) __builtin_amdgcn_s_sleep(127);
   }
-  load_first((long)k * T * R, true);
+  const long ctr0 = (long)k * T * R;   // this update's first column
   for (int t = 0; t < T; ++t) {
-    const long ctr = ((long)k * T + t) * R;
+    const long ctr = ctr0 + (long)t * R;
     BWD_STAMP(0);
     head_cot(t);
     lds_barrier();
     BWD_STAMP(1);
     BWD_WSTAMP(0);
-    floatx16 rc[3][2];   // BWD_TRECOMP: the recomputed r, z, W_hn h (+ b_hn) accumulators
-    if (BWD_TRECOMP) {
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) rc[g][h][q] = 0.0f;
-      f16x8 Ra0[3][2], Ra1[3][2], Rb[2][2];
-      const int ln = lane_now(), bl = (ln & 31) * PP + 8 * (ln >> 5);
-      auto ldRB = [&](int ks, int h) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) Rb[h][q] = *reinterpret_cast<const f16x8*>(&dgB[q][bl + RB * h * PP + 16 * ks]);
-      };
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          Ra0[g][q] = ldAh(0, g, q);
-          Ra1[g][q] = ldAh(1, g, q);
-        }
-      ldRB(0, 0);
-      ldRB(0, 1);
-      auto rstep = [&](int ks, f16x8 (&Ar)[3][2], bool reload) {
-#pragma unroll
-        for (int g = 0; g < 3; ++g) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            rc[g][h] = mfma3h(Ar[g], Rb[h], rc[g][h]);
-            if (g == 2 && ks + 1 < 16) ldRB(ks + 1, h);
-          }
-          if (reload) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) Ar[g][q] = ldAh(ks + 2, g, q);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      };
-#pragma nounroll
-      for (int kp = 0; kp < 7; ++kp) {
-        rstep(2 * kp, Ra0, true);
-        rstep(2 * kp + 1, Ra1, true);
-      }
-      rstep(14, Ra0, false);
-      rstep(15, Ra1, false);
-      lds_barrier();   // the image read before the memory part's f32 dr staging overwrites it
-    }
     // ---- memory part: the eight unit quads (two row tiles x four) as a software pipeline, quad i+1's five
     // 16-byte loads in flight while quad i is transposed and processed (twice the bytes in flight per wave)
     float dz_r[2][16], dhn_r[2][16];
@@ -2072,7 +1569,7 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
         st_u(rs, (unsigned)(((long)ub * p.M + r0 + RB * h + col) * 4),
              (unsigned)(((long)qunit(4 * g4 + e) * p.M + ctr) * 4), v[e]);
     };
-    load_first(ctr, false);
+    load_first(ctr);
     floatx16 ain;
     floatx16 hacc;
     float dx3 = 0.0f, dx4 = 0.0f;
@@ -2080,13 +1577,6 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #pragma unroll
     for (int qi = 0; qi < 8; ++qi) {
       const int h = qi >> 2, g4 = qi & 3;
-      // BWD_MPRIO (timing study): the two waves of a SIMD (w, w + 4) take turns at the higher issue priority, one quad
-      // each (1), or the younger wave leads (2), instead of the older wave leading the whole memory part
-      if (BWD_MPRIO == 1) {
-        if (((qi + (wave >> 2)) & 1) == 0) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
-      } else if (BWD_MPRIO == 2 && qi == 0) {
-        if (wave >= 4) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
-      }
       float (&v)[4][4] = vr[qi % NR];
       if (qi + NR - 1 < 8) load_q(ctr, (qi + NR - 1) >> 2, (qi + NR - 1) & 3, vr[(qi + NR - 1) % NR]);
       if (qi == 3) load_x(ctr, 1, xb);
@@ -2151,10 +1641,7 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #pragma unroll
       for (int jj = 0; jj < (BWD_PK ? 0 : 4); ++jj) {
         const int q = 4 * g4 + jj;
-        const float hin = v[0][jj];
-        const float rg = BWD_TRECOMP ? sigm_r(rc[0][h][q] * 0.5f) : v[1][jj];
-        const float zg = BWD_TRECOMP ? sigm_r(rc[1][h][q] * 0.5f) : v[2][jj];
-        const float hn = BWD_TRECOMP ? rc[2][h][q] * 0.5f : v[3][jj];
+        const float hin = v[0][jj], rg = v[1][jj], zg = v[2][jj], hn = v[3][jj];
         const float ng = gate_n(ain[q], rg, hn);
         const float hout = (1.0f - zg) * ng + zg * hin;
         const float d = dh[h][q] + (hout > 0.0f ? hacc[q] : 0.0f);
@@ -2188,7 +1675,6 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (BWD_MPRIO) __builtin_amdgcn_s_setprio(0);
     BWD_STAMP(2);
     BWD_WSTAMP(1);
     // row maxima of |dr|, |dz|, |dhn| over this wave's units (the fp16 B scale of the three passes)
@@ -2231,8 +1717,6 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     };
     // dr -> fp16 pieces: x0 straight into slot 0, x1 held until every lane has read its staged f32 values
     // (slot 1 overlaps the staging)
-    float qv[32];   // the pass's DG store queue (BWD_SPREAD): dr, then dz, then dhn, [h][4 g4 + e]
-    if (BWD_SPLACE) preload_ring(0);   // ahead of the dr stores below
     {
       f16x4 x1h[2][4];
 #pragma unroll
@@ -2246,12 +1730,7 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) split2h(v4[e] * bs[h], x0, x1h[h][g4], e);
           *reinterpret_cast<f16x4*>(&dgB[0][row * PP + un + 8 * g4]) = x0;
-          if (BWD_SPREAD) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) qv[16 * h + 4 * g4 + e] = v4[e];
-          } else {
-            store_dg(0, RB * h, g4, v4);
-          }
+          store_dg(0, RB * h, g4, v4);
         }
       lds_barrier();
 #pragma unroll
@@ -2276,62 +1755,23 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
     }
     BWD_STAMP(4);
     BWD_WSTAMP(2);
-    // BWD_INPASS: dz's first piece goes to the idle slot 2 during pass dr, dhn's to slot 1 (dr's second piece, read
-    // through) during pass dz; the refills write only the second pieces: pass dz reads slots (2, 0), pass dhn (1, 2)
-    auto inpass_put = [&](int j, int slot, const float (&src)[2][16]) {
-#pragma unroll
-      for (int i = 2 * j; i < 2 * j + 2; ++i) {   // (h, g4) = (i >> 2, i & 3): eight quads over the four k-steps
-        const int h = i >> 2, g4 = i & 3;
-        const float v4[4] = {src[h][4 * g4], src[h][4 * g4 + 1], src[h][4 * g4 + 2], src[h][4 * g4 + 3]};
-        put1h(slot, 0, rown(h), ubn() + 8 * g4, v4, bs[h]);
-      }
-    };
-    contract_h(0, 0, 1, qv, ctr, [] {}, (bool)BWD_SPLACE, BWD_SPLACE ? 1 : -1, [&] {
-      if (BWD_SPLACE) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const float v4[4] = {dz_r[h][4 * g4], dz_r[h][4 * g4 + 1], dz_r[h][4 * g4 + 2], dz_r[h][4 * g4 + 3]};
-            store_dg(1, RB * h, g4, v4);
-          }
-      }
-    }, [&](int j) {
-      if (BWD_INPASS) inpass_put(j, 2, dz_r);
-    });
+    contract_h(0);
     BWD_WSTAMP(3);
     lds_barrier();
     BWD_WSTAMP(4);
+    // the image refilled with dz, then dhn (held in registers since the memory part), with their DG stores
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const float v4[4] = {dz_r[h][4 * g4], dz_r[h][4 * g4 + 1], dz_r[h][4 * g4 + 2], dz_r[h][4 * g4 + 3]};
-        if (BWD_INPASS) put1h(0, 1, rown(h), ubn() + 8 * g4, v4, bs[h]);
-        else put4h(rown(h), ubn() + 8 * g4, v4, bs[h]);
-        if (BWD_SPREAD) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) qv[16 * h + 4 * g4 + e] = v4[e];
-        } else if (!BWD_SPLACE) {
-          store_dg(1, RB * h, g4, v4);
-        }
+        put4h(rown(h), ubn() + 8 * g4, v4, bs[h]);
+        store_dg(1, RB * h, g4, v4);
       }
     lds_barrier();
     BWD_STAMP(5);
     BWD_WSTAMP(5);
-    contract_h(1, BWD_INPASS ? 2 : 0, BWD_INPASS ? 0 : 1, qv, ctr, [] {}, (bool)BWD_SPLACE, BWD_SPLACE ? 2 : -1, [&] {
-      if (BWD_SPLACE) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const float v4[4] = {dhn_r[h][4 * g4], dhn_r[h][4 * g4 + 1], dhn_r[h][4 * g4 + 2], dhn_r[h][4 * g4 + 3]};
-            store_dg(2, RB * h, g4, v4);
-          }
-      }
-    }, [&](int j) {
-      if (BWD_INPASS) inpass_put(j, 1, dhn_r);
-    });
+    contract_h(1);
     BWD_WSTAMP(6);
     lds_barrier();
     BWD_WSTAMP(7);
@@ -2340,20 +1780,12 @@ __global__ void __launch_bounds__(512, 1) k_gru_bwd6n(BwdArgs p) {
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const float v4[4] = {dhn_r[h][4 * g4], dhn_r[h][4 * g4 + 1], dhn_r[h][4 * g4 + 2], dhn_r[h][4 * g4 + 3]};
-        if (BWD_INPASS) put1h(2, 1, rown(h), ubn() + 8 * g4, v4, bs[h]);
-        else put4h(rown(h), ubn() + 8 * g4, v4, bs[h]);
-        if (BWD_SPREAD) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) qv[16 * h + 4 * g4 + e] = v4[e];
-        } else if (!BWD_SPLACE) {
-          store_dg(2, RB * h, g4, v4);
-        }
+        put4h(rown(h), ubn() + 8 * g4, v4, bs[h]);
+        store_dg(2, RB * h, g4, v4);
       }
     lds_barrier();
     BWD_STAMP(6);
-    contract_h(2, BWD_INPASS ? 1 : 0, BWD_INPASS ? 2 : 1, qv, ctr, [&] {
-      if (t + 1 < T) load_first(ctr + R, true);
-    }, (bool)BWD_SPLACE, -1, [] {}, [](int) {});
+    contract_h(2);
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
       const float4 w4 = *reinterpret_cast<const float4*>(&wsc[32 * wave + 4 * (lane_now() >> 5) + 8 * g4]);
@@ -2587,8 +2019,6 @@ int toued_gru_bwd(int R, int T, int W, int K, const uint8_t* done, long done_str
 
 // 1 when the forward / backward for R rows keep r, z, W_hn h + b_hn in 32-column slab blocks (the split-precision pair)
 int toued_gru_slab_saves(int R) { return toued_gru_bwd_col_exp(R); }
-// 1 when the slab saves include h_in (A's first 256 rows' region; 0 only in HIN_SLAB=0 comparison builds)
-int toued_gru_hin_slab(void) { return HIN_SLAB; }
 
 // 1 when toued_gru_bwd_fused applies: the lockstep kernel (R a multiple of 64) with F + 10 <= 16 A rows
 int toued_gru_bwd_fused_fits(int R, int F) { return toued_gru_bwd_col_exp(R) && F >= 1 && F <= 6 ? 1 : 0; }
@@ -2679,9 +2109,6 @@ int toued_dbg_fwd_stamps(unsigned long long* host) {
 }
 int toued_dbg_fwd_gm_stamps(unsigned long long* host) {   // [64 workgroups][32 steps][4]
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fwd_gm), sizeof(g_fwd_gm)) == hipSuccess ? 0 : 1;
-}
-int toued_dbg_fwd_pp_stamps(unsigned long long* host) {   // [64 workgroups][32 steps][2 halves][6]
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fwd_pp), sizeof(g_fwd_pp)) == hipSuccess ? 0 : 1;
 }
 #endif
 
