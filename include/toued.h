@@ -510,6 +510,38 @@ int toued_entropy_clip_hvp(int N, int W, int T, int D, int K, const float* theta
                            float lr_c, float max_norm, float* coef, float alpha_y, float b2, float b3, float* d_pi_hat,
                            float* d_y_hat, hipStream_t stream);
 
+/* The meta-gradient step without a dense parameter history: one live pair of agent tables updated in place, plus
+ * per-update snapshots of the rows the reverse pass reads.
+ * toued_agent_step_snap is toued_agent_step_entropy with the output tables aliasing the inputs (every sample's rows
+ * are read before the first row write, and a row has one writer: the contract toued_agent_update and toued_hvp's
+ * in-place adjoint rely on); tables, Gth / Gph, met, step and gstat are bit-identical to toued_agent_step_entropy's
+ * theta1 / phi1 etc.  It also writes, contiguously in sample order s = t W + w,
+ *   snap_th0 [N][T W][5], snap_ph0 [N][(T+1) W][8]  theta_k / phi_k at row tidx[a][s] (phi also at the W bootstrap
+ *                                                   observations s = T W + w, which toued_embed_bwd_snap reads)
+ *   snap_last0 [N][16]                              the time rows theta_k[D-1] (0..4) and phi_k[D-1] (8..15)
+ *   snap_th1 [N][T W][5], snap_ph1 [N][T W][8], snap_last1 [N][16]   the same of theta_{k+1} / phi_{k+1}
+ * (the new rows are stored, not recomputed from the old row, G_k and gstat: one contiguous read per sample in the
+ * reverse pass instead of a second gather).  toued_entropy_clip_hvp_snap and toued_embed_bwd_snap are
+ * toued_entropy_clip_hvp and toued_embed_bwd reading those snapshots (of update k; toued_embed_bwd_snap all K:
+ * snap_ph [K][N][(T+1) W][8], snap_last [K][N][16]) in place of dense tables; bit-identical outputs. */
+int toued_agent_step_snap(int N, int W, int T, int D, float* theta, float* phi, const int* tidx, const int* ttime,
+                          const uint8_t* tact, const float* trew, const uint8_t* tdone, const float* pi_hat,
+                          const float* y_hat, float alpha_y, float lr_a, float lr_c, float max_norm, float* Gth,
+                          float* Gph, float* met, int* step, const int* levels, float* gstat, float* snap_th0,
+                          float* snap_ph0, float* snap_last0, float* snap_th1, float* snap_ph1, float* snap_last1,
+                          hipStream_t stream);
+int toued_entropy_clip_hvp_snap(int N, int W, int T, int D, int K, const float* snap_th1, const float* snap_ph1,
+                                const float* snap_last1, const float* snap_th0, const float* snap_ph0,
+                                const float* snap_last0, const int* tidx, const int* ttime, const uint8_t* tact,
+                                const float* pi_hat, const float* y_hat, float coef_a, float coef_c, float* adj_th,
+                                float* adj_ph, const float* Gth, const float* Gph, const float* gstat, float lr_a,
+                                float lr_c, float max_norm, float* coef, float alpha_y, float b2, float b3,
+                                float* d_pi_hat, float* d_y_hat, hipStream_t stream);
+int toued_embed_bwd_snap(int N, int W, int T, int D, int K, const float* snap_ph, const float* snap_last,
+                         const int* ttime_hist, long tidx_stride, const uint8_t* tdone_hist, long tstep_stride,
+                         const float* dX3, const float* dX4, long dx_stride_k, const float* e1w, const float* e1b,
+                         const float* e2w, float* partial, int n_blocks, hipStream_t stream);
+
 /* ES inference path: pack n candidates' forward fragments (candidate c at eta + c*eta_stride) */
 int toued_gru_pack_fwd_multi(const float* eta, long eta_stride, int n, const int* off, int F, float* fwdA,
                              hipStream_t stream);

@@ -55,6 +55,27 @@ TOUED_DEV void probs_of(const float* __restrict__ tab, const float* __restrict__
   for (int j = 0; j < K; ++j) p[j] *= inv;
 }
 
+// probs_of on a row already in registers (the same operations in the same order: bit-identical)
+template <int K>
+TOUED_DEV void probs_regs(const float* row, const float* last, float c, float* p) {
+  float l[K];
+  float m = -__builtin_inff();
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    l[j] = row[j] + c * last[j];
+    m = fmaxf(m, l[j]);
+  }
+  float s = 0.0f;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    p[j] = __expf(l[j] - m);
+    s += p[j];
+  }
+  const float inv = 1.0f / s;
+#pragma unroll
+  for (int j = 0; j < K; ++j) p[j] *= inv;
+}
+
 // base[elem] with a 32-bit byte offset: a load (or store) off a uniform base pointer takes the scalar-base form
 // (one offset register, no 64-bit address pair per table)
 template <class T>
@@ -553,10 +574,15 @@ TOUED_DEV void entropy_metric_agent(int a, int tid, int W, int T, int D, const f
 // entropy_metric_agent for a 512-thread block with T*W * 13 floats of LDS (`terms`): all 512 threads compute the
 // samples' 13 entropy terms (p + eps) log(p + eps) into LDS, then the same 256 threads as entropy_metric_agent
 // subtract them in the same order -- the same values and sums, with half the dependent gathers per thread
+// SNAP (toued_agent_step_snap): the rows it reads -- theta_{k+1} / phi_{k+1} at the rollout's samples and the time
+// rows -- also go out contiguously in sample order (s1_th [N][T W][5], s1_ph [N][T W][8], s1_last [N][16]: theta's
+// time row at 0..4, phi's at 8..15) for the reverse pass; the same row values through probs_regs (bit-identical)
+template <bool SNAP = false>
 TOUED_DEV void entropy_metric_block(int a, int tid, int W, int T, int D, const float* __restrict__ theta,
                                     const float* __restrict__ phi, const int* __restrict__ tidx,
                                     const int* __restrict__ ttime, float* __restrict__ met, float (*red)[4],
-                                    float* terms) {
+                                    float* terms, float* __restrict__ s1_th = nullptr,
+                                    float* __restrict__ s1_ph = nullptr, float* __restrict__ s1_last = nullptr) {
   const int TW = T * W;
   {
     const float* th = theta + (size_t)a * D * 5;
@@ -566,6 +592,14 @@ TOUED_DEV void entropy_metric_block(int a, int tid, int W, int T, int D, const f
     for (int j = 0; j < 5; ++j) lastA[j] = th[(size_t)(D - 1) * 5 + j];
 #pragma unroll
     for (int j = 0; j < 8; ++j) lastC[j] = ph[(size_t)(D - 1) * 8 + j];
+    if constexpr (SNAP) {
+      if (tid == 0) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) s1_last[(size_t)a * 16 + j] = lastA[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s1_last[(size_t)a * 16 + 8 + j] = lastC[j];
+      }
+    }
     const int* ti = tidx + (size_t)a * (T + 1) * W;   // sample i = t W + w
     const int* tt = ttime + (size_t)a * (T + 1) * W;
     // the thread's (at most four: T W <= 2048) samples' indices first, then their row gathers: two dependent trips
@@ -582,8 +616,24 @@ TOUED_DEV void entropy_metric_block(int a, int tid, int W, int T, int D, const f
       const int i = tid + 512 * q;
       if (i < TW) {
         float p[5], y[8];
-        probs_of<5>(th, lastA, ix[q], cx[q], p);
-        probs_of<8>(ph, lastC, ix[q], cx[q], y);
+        if constexpr (SNAP) {
+          float ra[5], rc[8];
+#pragma unroll
+          for (int j = 0; j < 5; ++j) ra[j] = ldrow(th, (unsigned)ix[q] * 20u, j);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) rc[j] = ldrow(ph, (unsigned)ix[q] * 32u, j);
+          float* oa = s1_th + ((size_t)a * TW + i) * 5;
+          float* oc = s1_ph + ((size_t)a * TW + i) * 8;
+#pragma unroll
+          for (int j = 0; j < 5; ++j) oa[j] = ra[j];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) oc[j] = rc[j];
+          probs_regs<5>(ra, lastA, cx[q], p);
+          probs_regs<8>(rc, lastC, cx[q], y);
+        } else {
+          probs_of<5>(th, lastA, ix[q], cx[q], p);
+          probs_of<8>(ph, lastC, ix[q], cx[q], y);
+        }
         float* e = terms + (size_t)i * 13;
 #pragma unroll
         for (int j = 0; j < 5; ++j) e[j] = (p[j] + EPSF) * __logf(p[j] + EPSF);
@@ -950,27 +1000,6 @@ __global__ void __launch_bounds__(256) k_hvp(int N, int W, int T, int D, int K, 
 // grad layout (161 floats): e1_b[16], e1_w[8*16], e2_b[1], e2_w[16] (flat-eta order within MLP_0)
 // Inputs: y_t / y_tp1 recomputed from phi_k; cotangents dX3 (pyt), dX4 (pyt1, masked by done).
 
-// probs_of on a row already in registers (the same operations in the same order: bit-identical)
-template <int K>
-TOUED_DEV void probs_regs(const float* row, const float* last, float c, float* p) {
-  float l[K];
-  float m = -__builtin_inff();
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    l[j] = row[j] + c * last[j];
-    m = fmaxf(m, l[j]);
-  }
-  float s = 0.0f;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    p[j] = __expf(l[j] - m);
-    s += p[j];
-  }
-  const float inv = 1.0f / s;
-#pragma unroll
-  for (int j = 0; j < K; ++j) p[j] *= inv;
-}
-
 // One lane per sample and the e1_w / e1_b reduction on the matrix cores; partial[block][161] in the flat layout above.
 // A wave takes 64 consecutive samples per round (each load instruction covers 64 samples: 256 contiguous bytes of an
 // index or cotangent array; a quad-per-sample layout covered 16 and repeated the loads and the softmax in four lanes);
@@ -980,14 +1009,17 @@ TOUED_DEV void probs_regs(const float* row, const float* last, float c, float* p
 // A^T D over the 64 items into a 16 x 16 accumulator (rows 0..7 e1_w, row 8 e1_b) -- 4 accumulator registers
 // instead of 41 per lane, so the kernel runs at 6 waves per SIMD.  The next round's index / time / cotangent loads
 // are issued before this round's maths.  f32 products and sums.
-template <bool UNIF>
+// SNAP (toued_embed_bwd_snap): phi_hist is toued_agent_step_snap's phi_k row snapshots [K][N][(T+1) W][8] (sample
+// t W + w and its successor W further on), last_hist [K][N][16] the time rows (phi's at 8..15); no index loads.
+template <bool UNIF, bool SNAP = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EMBED_WPE))) k_embed_bwd3(int N, int W, int T, int D, int K, const float* __restrict__ phi_hist,
                                                     long phi_stride, int phi_slot0, const int* __restrict__ tidx_hist, long tidx_stride,
                                                     const int* __restrict__ ttime_hist, const uint8_t* __restrict__ tdone_hist,
                                                     long tstep_stride, const float* __restrict__ dX3,
                                                     const float* __restrict__ dX4, long dx_stride_k,
                                                     const float* __restrict__ e1w, const float* __restrict__ e1b,
-                                                    const float* __restrict__ e2w, float* __restrict__ partial) {
+                                                    const float* __restrict__ e2w, float* __restrict__ partial,
+                                                    const float* __restrict__ last_hist) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   __shared__ float4 sw1[8][4];                   // e1_w [8][16] as float4 rows of four units
   __shared__ float4 sb1[4], sw2[4];              // e1_b, e2_w
@@ -1011,6 +1043,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EMBED_
   const int stride = gridDim.x * blockDim.x;     // samples per round of the grid
   struct In {
     const float* ph;
+    const float* lastp;   // SNAP only
     int ix[2];
     float cx[2], cg[2];
   };
@@ -1028,12 +1061,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EMBED_
     const int* tidx = tidx_hist + k * tidx_stride;
     const int* ttime = ttime_hist + k * tidx_stride;
     const uint8_t* tdone = tdone_hist + k * tstep_stride;
-    const int slot = k + phi_slot0 > K ? k + phi_slot0 - (K + 1) : k + phi_slot0;   // ring of K + 1 slots
-    v.ph = phi_hist + slot * phi_stride + (size_t)a * D * 8;
     const size_t o0 = ((size_t)a * (T + 1) + t) * W + w;
     const size_t o = (size_t)k * dx_stride_k + (size_t)t * R + r;
-    v.ix[0] = tidx[o0];
-    v.ix[1] = tidx[o0 + W];
+    if constexpr (SNAP) {
+      v.ph = phi_hist + ((size_t)k * N + a) * (size_t)(T + 1) * W * 8;
+      v.lastp = last_hist + ((size_t)k * N + a) * 16 + 8;
+      v.ix[0] = t * W + w;
+      v.ix[1] = v.ix[0] + W;
+    } else {
+      const int slot = k + phi_slot0 > K ? k + phi_slot0 - (K + 1) : k + phi_slot0;   // ring of K + 1 slots
+      v.ph = phi_hist + slot * phi_stride + (size_t)a * D * 8;
+      v.lastp = nullptr;
+      v.ix[0] = tidx[o0];
+      v.ix[1] = tidx[o0 + W];
+    }
     v.cx[0] = (float)ttime[o0] * 0.001f;
     v.cx[1] = (float)ttime[o0 + W] * 0.001f;
     v.cg[0] = live ? dX3[o] : 0.0f;
@@ -1054,7 +1095,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(EMBED_
     nx = load_in(gb + lane + stride);
     float last[8], row[2][8];
     {
-      const float4* lp = reinterpret_cast<const float4*>(cur.ph + (size_t)(D - 1) * 8);
+      const float4* lp = reinterpret_cast<const float4*>(SNAP ? cur.lastp : cur.ph + (size_t)(D - 1) * 8);
       const float4 l0 = lp[0], l1 = lp[1];
       last[0] = l0.x; last[1] = l0.y; last[2] = l0.z; last[3] = l0.w;
       last[4] = l1.x; last[5] = l1.y; last[6] = l1.z; last[7] = l1.w;
@@ -1250,17 +1291,22 @@ struct GradOp {   // k_agent_grad (+ the global norms and the lifetime test of t
     return i < 5 ? theta[((size_t)a * D + D - 1) * 5 + i] : phi[((size_t)a * D + D - 1) * 8 + (i - 5)];
   }
   TOUED_DEV bool sample(int a, int t, int w, int idx, float c, float* v, float* m, const float* lastv) const {
-    const long s = ((long)a * T + t) * W + w;
-    const int R = N * W;
-    const int qr = a * W + w, qact = tact[s];
-    const float inv_wt = 1.0f / (float)(W * T);
     const float* th = theta + (size_t)a * D * 5;
     const float* ph = phi + (size_t)a * D * 8;
     const float* lastA = lastv;
     const float* lastC = lastv + 5;
-    float p[5], y[8], yh[8];
+    float p[5], y[8];
     probs_of<5>(th, lastA, idx, c, p);
     probs_of<8>(ph, lastC, idx, c, y);
+    return sample_py(a, t, w, p, y, v, m);
+  }
+  // the sample's row cotangents and metric terms from its policy p and target distribution y
+  TOUED_DEV bool sample_py(int a, int t, int w, const float* p, const float* y, float* v, float* m) const {
+    const long s = ((long)a * T + t) * W + w;
+    const int R = N * W;
+    const int qr = a * W + w, qact = tact[s];
+    const float inv_wt = 1.0f / (float)(W * T);
+    float yh[8];
     const size_t o = (size_t)t * R + qr;
     const float pih = pi_hat[o];
 #pragma unroll
@@ -1314,6 +1360,59 @@ struct GradStepOp : GradApplyOp {
 struct GradStepEntOp : GradStepOp {
   static constexpr bool ENTROPY_AFTER = true;
 };
+
+// toued_agent_step_snap: GradStepEntOp IN PLACE (theta_w / phi_w are theta / phi: the block reads every sample's rows
+// in phase 1, before the sort's barriers; after them a row is read (srcv) and rewritten by its one owner thread only,
+// the contract toued_agent_update and toued_hvp's in-place adjoint already rely on), leaving the reverse pass what it
+// reads of the overwritten tables as contiguous per-sample snapshots:
+//   s0_th [N][T W][5], s0_ph [N][(T+1) W][8]  theta_k / phi_k rows of the samples, in sample order (phi also at the
+//                                             bootstrap observations t = T, which toued_embed_bwd reads)
+//   s0_last [N][16]                           the time rows theta_k[D-1] (0..4), phi_k[D-1] (8..15)
+//   s1_th [N][T W][5], s1_ph [N][T W][8], s1_last [N][16]   the same of theta_{k+1} / phi_{k+1} (written by the
+//                                             entropy phase, which gathers exactly these rows)
+struct GradStepSnapOp : GradStepEntOp {
+  static constexpr bool SNAP_ROWS = true;
+  float* s0_th; float* s0_ph; float* s0_last; float* s1_th; float* s1_ph; float* s1_last;
+  // before the block's first barrier: the time rows and phi_k at the W bootstrap observations
+  TOUED_DEV void snap_prologue(int a, int tid) const {
+    if (tid < 13) s0_last[(size_t)a * 16 + (tid < 5 ? tid : tid + 3)] = last_val(a, tid);
+    const int TW = T * W;
+    const float* ph = phi + (size_t)a * D * 8;
+    for (int sl = TW + tid; sl < TW + W; sl += 512) {
+      const unsigned ix = (unsigned)ld32(tidx + (size_t)a * (T + 1) * W, (unsigned)sl);
+      float rc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rc[j] = ldrow(ph, ix * 32u, j);
+      float* oc = s0_ph + ((size_t)a * (TW + W) + sl) * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) oc[j] = rc[j];
+    }
+  }
+  TOUED_DEV bool sample(int a, int t, int w, int idx, float c, float* v, float* m, const float* lastv) const {
+    const float* th = theta + (size_t)a * D * 5;
+    const float* ph = phi + (size_t)a * D * 8;
+    const int TW = T * W, sl = t * W + w;
+    float ra[5], rc[8];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) ra[j] = ldrow(th, (unsigned)idx * 20u, j);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rc[j] = ldrow(ph, (unsigned)idx * 32u, j);
+    float* oa = s0_th + ((size_t)a * TW + sl) * 5;
+    float* oc = s0_ph + ((size_t)a * (TW + W) + sl) * 8;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) oa[j] = ra[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oc[j] = rc[j];
+    float p[5], y[8];
+    probs_regs<5>(ra, lastv, c, p);
+    probs_regs<8>(rc, lastv + 5, c, y);
+    return sample_py(a, t, w, p, y, v, m);
+  }
+};
+template <class Op, class = void>
+struct snap_rows : std::false_type {};
+template <class Op>
+struct snap_rows<Op, std::void_t<decltype(Op::SNAP_ROWS)>> : std::bool_constant<Op::SNAP_ROWS> {};
 // ops whose sample is register-heavy accumulate the time row's partial sums after the sample loop (HvpOp)
 template <class Op, class = void>
 struct defer_time_row : std::false_type {};
@@ -1324,24 +1423,42 @@ struct entropy_after : std::false_type {};
 template <class Op>
 struct entropy_after<Op, std::void_t<decltype(Op::ENTROPY_AFTER)>> : std::bool_constant<Op::ENTROPY_AFTER> {};
 
-struct EntropyBwdOp {   // k_entropy, gradient mode
+// SNAP (the reverse pass over toued_agent_step_snap's snapshots): theta / phi are the per-sample row snapshots
+// [N][T W][5] / [N][T W][8] of the tables at the rollout's samples, tlast [N][16] their time rows (0..4, 8..15);
+// the rows come in with contiguous loads in sample order instead of gathers into a dense table, same values
+template <bool SNAP>
+struct EntropyBwdOpT {   // k_entropy, gradient mode
   static constexpr int NA = 5, NC = 8, NM = 1;
   static constexpr bool NORMS = false, APPLY = false, WRITE_G = false, CLIPDOT = false;
   const float* theta; const float* phi; const int* tidx; const int* ttime; float coef_a, coef_c;
   float* adj_th; float* adj_ph;
   int N, W, T, D;
+  const float* tlast = nullptr;
   static constexpr int NLAST = 13;   // the time rows theta[D-1], phi[D-1]: the same for every sample of the agent
   TOUED_DEV float last_val(int a, int i) const {
+    if constexpr (SNAP) return tlast[(size_t)a * 16 + (i < 5 ? i : i + 3)];
     return i < 5 ? theta[((size_t)a * D + D - 1) * 5 + i] : phi[((size_t)a * D + D - 1) * 8 + (i - 5)];
   }
   TOUED_DEV bool sample(int a, int t, int w, int idx, float c, float* v, float* m, const float* lastv) const {
-    const float* th = theta + (size_t)a * D * 5;
-    const float* ph = phi + (size_t)a * D * 8;
     const float* lastA = lastv;
     const float* lastC = lastv + 5;
     float p[5], y[8];
-    probs_of<5>(th, lastA, idx, c, p);
-    probs_of<8>(ph, lastC, idx, c, y);
+    if constexpr (SNAP) {
+      const unsigned sl = (unsigned)(t * W + w);
+      const size_t tw = (size_t)a * T * W;
+      float ra[5], rc[8];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) ra[j] = ldrow(theta + tw * 5, sl * 20u, j);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rc[j] = ldrow(phi + tw * 8, sl * 32u, j);
+      probs_regs<5>(ra, lastA, c, p);
+      probs_regs<8>(rc, lastC, c, y);
+    } else {
+      const float* th = theta + (size_t)a * D * 5;
+      const float* ph = phi + (size_t)a * D * 8;
+      probs_of<5>(th, lastA, idx, c, p);
+      probs_of<8>(ph, lastC, idx, c, y);
+    }
     float ga[5], gc[8];
 #pragma unroll
     for (int j = 0; j < 5; ++j) ga[j] = -(__logf(p[j] + EPSF) + 1.0f);
@@ -1365,17 +1482,20 @@ struct EntropyBwdOp {   // k_entropy, gradient mode
   TOUED_DEV void metrics(int, const float*) const {}
   TOUED_DEV void finish(int, float, float) const {}
 };
+using EntropyBwdOp = EntropyBwdOpT<false>;
 
 // EntropyBwdOp of the reverse pass's step k fused with the clip-VJP dot that follows it: the rows it rewrites are
 // exactly the rows update k touched (the same trajectory, plus the time row), so the thread owning a row adds
 // <G_k[row], adjoint[row]> as it writes the row, and thread 0 turns the block's sums into coef (k_clip_dot's
 // coefficients up to the summation order: the untouched rows, zero in the dense tables, are not visited)
-struct EntropyClipOp : EntropyBwdOp {
+template <bool SNAP>
+struct EntropyClipOpT : EntropyBwdOpT<SNAP> {
   static constexpr bool CLIPDOT = true;
   const float* Gth; const float* Gph; const float* gstat; float lr_a, lr_c, max_norm; float* coef;
-  TOUED_DEV float gA(int a, int r, int j) const { return Gth[((size_t)a * D + r) * 5 + j]; }
-  TOUED_DEV float gC(int a, int r, int j) const { return Gph[((size_t)a * D + r) * 8 + j]; }
+  TOUED_DEV float gA(int a, int r, int j) const { return Gth[((size_t)a * this->D + r) * 5 + j]; }
+  TOUED_DEV float gC(int a, int r, int j) const { return Gph[((size_t)a * this->D + r) * 8 + j]; }
 };
+using EntropyClipOp = EntropyClipOpT<false>;
 
 struct LpgLossOp {   // k_lpgloss_grad
   static constexpr int NA = 5, NC = 0, NM = 1;
@@ -1407,7 +1527,10 @@ struct LpgLossOp {   // k_lpgloss_grad
   TOUED_DEV void finish(int, float, float) const {}
 };
 
-struct HvpOp {   // k_hvp
+// SNAP: theta / phi are toued_agent_step_snap's theta_k / phi_k row snapshots [N][T W][5] / [N][(T+1) W][8], tlast
+// [N][16] their time rows (as EntropyBwdOpT); the adjoint and gradient tables stay dense
+template <bool SNAP>
+struct HvpOpT {   // k_hvp
   static constexpr int NA = 5, NC = 8, NM = 0;   // (no metrics)
   static constexpr bool DEFER_TIME_ROW = true;
   static constexpr bool NORMS = false, APPLY = false, WRITE_G = false, CLIPDOT = false;
@@ -1416,11 +1539,15 @@ struct HvpOp {   // k_hvp
   const float* adj_ph_in; const float* coef; float lr_a, lr_c, alpha_y, b2, b3;
   float* adj_th_out; float* adj_ph_out; float* d_pi_hat; float* d_y_hat;
   int N, W, T, D, K;
+  const float* tlast = nullptr;
   // per-agent values every sample reads: theta[D-1] (0..4), phi[D-1] (5..12), adj_th_in[D-1] (13..17),
   // Gth[D-1] (18..22), adj_ph_in[D-1] (23..30), Gph[D-1] (31..38), coef[a] (39..42)
   static constexpr int NLAST = 43;
   TOUED_DEV float last_val(int a, int i) const {
     const size_t rA = ((size_t)a * D + D - 1) * 5, rC = ((size_t)a * D + D - 1) * 8;
+    if constexpr (SNAP) {
+      if (i < 13) return tlast[(size_t)a * 16 + (i < 5 ? i : i + 3)];
+    }
     if (i < 5) return theta[rA + i];
     if (i < 13) return phi[rC + (i - 5)];
     if (i < 18) return adj_th_in[rA + (i - 13)];
@@ -1449,7 +1576,7 @@ struct HvpOp {   // k_hvp
       float thr[5], adA[5], gA[5];
 #pragma unroll
       for (int j = 0; j < 5; ++j) {
-        thr[j] = ldrow(theta + baseA, bA, j);
+        thr[j] = SNAP ? ldrow(theta + (size_t)a * T * W * 5, tw * 20u, j) : ldrow(theta + baseA, bA, j);
         adA[j] = ldrow(adj_th_in + baseA, bA, j);
         gA[j] = ldrow(Gth + baseA, bA, j);
       }
@@ -1491,7 +1618,7 @@ struct HvpOp {   // k_hvp
       float phr[8], adC[8], gC[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        phr[j] = ldrow(phi + baseC, bC, j);
+        phr[j] = SNAP ? ldrow(phi + (size_t)a * (T + 1) * W * 8, tw * 32u, j) : ldrow(phi + baseC, bC, j);
         adC[j] = ldrow(adj_ph_in + baseC, bC, j);
         gC[j] = ldrow(Gph + baseC, bC, j);
       }
@@ -1531,6 +1658,7 @@ struct HvpOp {   // k_hvp
   TOUED_DEV void metrics(int, const float*) const {}
   TOUED_DEV void finish(int, float, float) const {}
 };
+using HvpOp = HvpOpT<false>;
 
 #ifndef ROWS_PRIO
 #define ROWS_PRIO 3   // C2 20.29-20.31 ms at 0, 19.96-20.00 at 3 (profiles/r04/c2_rows_prio_r04j.txt)
@@ -1609,6 +1737,7 @@ TOUED_DEV void rows_sorted_body(const Op& op) {
   }
   if (tid == 0) { has_last = 0; any_kept = 0; }
   if (tid < Op::NLAST) lastv[tid] = op.last_val(a, tid);
+  if constexpr (snap_rows<Op>::value) op.snap_prologue(a, tid);
 #ifdef ROWS_STAMPS
   unsigned rs_launch = 0;
 #endif
@@ -1954,8 +2083,12 @@ TOUED_DEV void rows_sorted_body(const Op& op) {
   if constexpr (entropy_after<Op>::value) {
     __syncthreads();   // the rewritten rows (and red's last readers) before the entropies read them
     static_assert(NVP == 13, "entropy_metric_block keeps 13 terms per sample in the row-vector area");
-    entropy_metric_block(a, tid, W, T, D, op.theta_w, op.phi_w, op.tidx, op.ttime, op.met,
-                         reinterpret_cast<float (*)[4]>(&red[0][0]), vec);
+    if constexpr (snap_rows<Op>::value)
+      entropy_metric_block<true>(a, tid, W, T, D, op.theta_w, op.phi_w, op.tidx, op.ttime, op.met,
+                                 reinterpret_cast<float (*)[4]>(&red[0][0]), vec, op.s1_th, op.s1_ph, op.s1_last);
+    else
+      entropy_metric_block(a, tid, W, T, D, op.theta_w, op.phi_w, op.tidx, op.ttime, op.met,
+                           reinterpret_cast<float (*)[4]>(&red[0][0]), vec);
   }
   ROWS_STAMP(6);
 }
@@ -2017,6 +2150,8 @@ static bool launch_sorted2(const Op1& op1, const Op2& op2, int N, hipStream_t st
 
 static inline unsigned nb256(long n) { return (unsigned)((n + 255) / 256); }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// HvpOp addresses pi_hat / y_hat / d_y_hat [T][8][N W] through 32-bit byte offsets (its largest: 32 N T W)
+static inline bool hvp_offsets_fit(int N, int W, int T) { return 32L * N * T * W < (1L << 32); }
 
 extern "C" {
 
@@ -2170,8 +2305,40 @@ int toued_agent_step_entropy(int N, int W, int T, int D, const float* theta, con
                     lr_c, max_norm, Gth, Gph, met, step, levels, gstat, true, stream);
 }
 
-// toued_entropy's gradient mode followed by toued_clip_dot over the touched rows, in one kernel (the reverse pass of toued_agent_step's
-// update k: Gth / Gph hold that update's touched rows, which are the rows this trajectory's entropy gradient writes)
+// toued_agent_step_entropy IN PLACE on theta / phi (no copy of the tables beforehand: the output tables alias the
+// inputs, see GradStepSnapOp for the contract), writing what the reverse pass reads of the overwritten tables as
+// per-sample snapshots: snap_th0 [N][T W][5], snap_ph0 [N][(T+1) W][8], snap_last0 [N][16] (theta_k / phi_k) and
+// snap_th1 [N][T W][5], snap_ph1 [N][T W][8], snap_last1 [N][16] (theta_{k+1} / phi_{k+1}).  Tables, Gth / Gph, met,
+// step and gstat as toued_agent_step_entropy leaves them in theta1 / phi1 (bit-identical).
+int toued_agent_step_snap(int N, int W, int T, int D, float* theta, float* phi, const int* tidx, const int* ttime,
+                          const uint8_t* tact, const float* trew, const uint8_t* tdone, const float* pi_hat,
+                          const float* y_hat, float alpha_y, float lr_a, float lr_c, float max_norm, float* Gth,
+                          float* Gph, float* met, int* step, const int* levels, float* gstat, float* snap_th0,
+                          float* snap_ph0, float* snap_last0, float* snap_th1, float* snap_ph1, float* snap_last1,
+                          hipStream_t stream) {
+  TOUED_REQUIRE(step && levels && gstat && met && Gth && Gph && theta && phi,
+                "toued_agent_step_snap: every output is required");
+  TOUED_REQUIRE(snap_th0 && snap_ph0 && snap_last0 && snap_th1 && snap_ph1 && snap_last1,
+                "toued_agent_step_snap: every snapshot is required");
+  TOUED_REQUIRE(toued_agent_update_fits(W, T, D), "toued_agent_step_snap: W=%d T=%d D=%d unsupported (T*W <= %d)", W, T,
+                D, SORT_MAX_TW);
+  if (N == 0) return 0;
+  GradStepSnapOp op;
+  static_cast<GradOp&>(op) = GradOp{theta, phi, tidx, ttime, tact, trew, tdone, pi_hat, y_hat, alpha_y, Gth, Gph,
+                                    met, step, levels, gstat, N, W, T, D};
+  op.theta_w = theta;   // in place
+  op.phi_w = phi;
+  op.lr_a = lr_a;
+  op.lr_c = lr_c;
+  op.max_norm = max_norm;
+  op.step_w = step;
+  op.s0_th = snap_th0; op.s0_ph = snap_ph0; op.s0_last = snap_last0;
+  op.s1_th = snap_th1; op.s1_ph = snap_ph1; op.s1_last = snap_last1;
+  TOUED_REQUIRE(launch_sorted(op, N, stream), "toued_agent_step_snap: cannot launch the sorted kernel");
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
 int toued_meta_metrics(int N, int K, const float* met, float inv_wt, const float* loss_out, float pec, float pl2,
                        float tec, float tl2, float* out, hipStream_t stream) {
   if (N == 0) return 0;
@@ -2182,6 +2349,9 @@ int toued_meta_metrics(int N, int K, const float* met, float inv_wt, const float
   return 0;
 }
 
+// toued_entropy's gradient mode followed by toued_clip_dot over the touched rows, in one kernel (the reverse pass of
+// toued_agent_step's update k: Gth / Gph hold that update's touched rows, which are the rows this trajectory's
+// entropy gradient writes)
 int toued_entropy_clip(int N, int W, int T, int D, const float* theta, const float* phi, const int* tidx,
                        const int* ttime, float coef_a, float coef_c, float* adj_th, float* adj_ph, const float* Gth,
                        const float* Gph, const float* gstat, float lr_a, float lr_c, float max_norm, float* coef,
@@ -2212,6 +2382,8 @@ int toued_entropy_clip_hvp(int N, int W, int T, int D, int K, const float* theta
                            float lr_c, float max_norm, float* coef, float alpha_y, float b2, float b3, float* d_pi_hat,
                            float* d_y_hat, hipStream_t stream) {
   TOUED_REQUIRE(toued_agent_update_fits(W, T, D), "toued_entropy_clip_hvp: W=%d T=%d D=%d unsupported", W, T, D);
+  TOUED_REQUIRE(hvp_offsets_fit(N, W, T), "toued_entropy_clip_hvp: 32*N*T*W = %ld bytes exceed the 32-bit offsets",
+                32L * N * T * W);
   if (N == 0) return 0;
   EntropyClipOp ec;
   static_cast<EntropyBwdOp&>(ec) = EntropyBwdOp{theta1, phi1, tidx, ttime, coef_a, coef_c, adj_th, adj_ph, N, W, T, D};
@@ -2225,6 +2397,40 @@ int toued_entropy_clip_hvp(int N, int W, int T, int D, int K, const float* theta
   const HvpOp hv{theta, phi, tidx, ttime, tact, pi_hat, y_hat, Gth, Gph, adj_th, adj_ph, coef, lr_a, lr_c, alpha_y,
                  b2, b3, adj_th, adj_ph, d_pi_hat, d_y_hat, N, W, T, D, K};
   TOUED_REQUIRE(launch_sorted2(ec, hv, N, stream), "toued_entropy_clip_hvp: cannot launch the sorted kernel");
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
+// toued_entropy_clip_hvp over toued_agent_step_snap's snapshots of update k instead of dense theta_{k+1} / theta_k
+// tables: (snap_th1, snap_ph1, snap_last1) are theta_{k+1} / phi_{k+1} at rollout k's samples, (snap_th0, snap_ph0,
+// snap_last0) theta_k / phi_k.  The same row values in the same operations (bit-identical); the adjoint and gradient
+// tables stay dense.
+int toued_entropy_clip_hvp_snap(int N, int W, int T, int D, int K, const float* snap_th1, const float* snap_ph1,
+                                const float* snap_last1, const float* snap_th0, const float* snap_ph0,
+                                const float* snap_last0, const int* tidx, const int* ttime, const uint8_t* tact,
+                                const float* pi_hat, const float* y_hat, float coef_a, float coef_c, float* adj_th,
+                                float* adj_ph, const float* Gth, const float* Gph, const float* gstat, float lr_a,
+                                float lr_c, float max_norm, float* coef, float alpha_y, float b2, float b3,
+                                float* d_pi_hat, float* d_y_hat, hipStream_t stream) {
+  TOUED_REQUIRE(toued_agent_update_fits(W, T, D), "toued_entropy_clip_hvp_snap: W=%d T=%d D=%d unsupported", W, T, D);
+  TOUED_REQUIRE(hvp_offsets_fit(N, W, T), "toued_entropy_clip_hvp_snap: 32*N*T*W = %ld bytes exceed the 32-bit offsets",
+                32L * N * T * W);
+  TOUED_REQUIRE(snap_th1 && snap_ph1 && snap_last1 && snap_th0 && snap_ph0 && snap_last0,
+                "toued_entropy_clip_hvp_snap: every snapshot is required");
+  if (N == 0) return 0;
+  EntropyClipOpT<true> ec;
+  static_cast<EntropyBwdOpT<true>&>(ec) =
+      EntropyBwdOpT<true>{snap_th1, snap_ph1, tidx, ttime, coef_a, coef_c, adj_th, adj_ph, N, W, T, D, snap_last1};
+  ec.Gth = Gth;
+  ec.Gph = Gph;
+  ec.gstat = gstat;
+  ec.lr_a = lr_a;
+  ec.lr_c = lr_c;
+  ec.max_norm = max_norm;
+  ec.coef = coef;
+  const HvpOpT<true> hv{snap_th0, snap_ph0, tidx, ttime, tact, pi_hat, y_hat, Gth, Gph, adj_th, adj_ph, coef, lr_a,
+                        lr_c, alpha_y, b2, b3, adj_th, adj_ph, d_pi_hat, d_y_hat, N, W, T, D, K, snap_last0};
+  TOUED_REQUIRE(launch_sorted2(ec, hv, N, stream), "toued_entropy_clip_hvp_snap: cannot launch the sorted kernel");
   TOUED_CHECK_LAUNCH();
   return 0;
 }
@@ -2313,6 +2519,7 @@ int toued_hvp(int N, int W, int T, int D, int K, const float* theta, const float
               float* d_y_hat, hipStream_t stream) {
   const long n = (long)N * T * W;
   if (n == 0) return 0;
+  TOUED_REQUIRE(hvp_offsets_fit(N, W, T), "toued_hvp: 32*N*T*W = %ld bytes exceed the 32-bit offsets", 32L * N * T * W);
   {
     HvpOp op{theta, phi, tidx, ttime, tact, pi_hat, y_hat, Gth, Gph, adj_th_in, adj_ph_in, coef, lr_a, lr_c, alpha_y,
              b2, b3, adj_th_out, adj_ph_out, d_pi_hat, d_y_hat, N, W, T, D, K};
@@ -2343,8 +2550,27 @@ int toued_embed_bwd(int N, int W, int T, int D, int K, const float* phi_hist, lo
 #define L_(KER) hipLaunchKernelGGL(KER, dim3(n_blocks), dim3(256), 0, stream, N, W, T, D, K, phi_hist, phi_stride,     \
                                    phi_slot0,                                                                       \
                                    tidx_hist, tidx_stride, ttime_hist, tdone_hist, tstep_stride, dX3, dX4, dx_stride_k, \
-                                   e1w, e1b, e2w, partial)
+                                   e1w, e1b, e2w, partial, (const float*)nullptr)
   if (W % 64 == 0) L_(k_embed_bwd3<true>); else L_(k_embed_bwd3<false>);
+#undef L_
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
+// toued_embed_bwd reading phi_k at the samples from toued_agent_step_snap's snapshots (snap_ph [K][N][(T+1) W][8],
+// snap_last [K][N][16]) instead of a dense history: the same rows, contiguous (bit-identical partials)
+int toued_embed_bwd_snap(int N, int W, int T, int D, int K, const float* snap_ph, const float* snap_last,
+                         const int* ttime_hist, long tidx_stride, const uint8_t* tdone_hist, long tstep_stride,
+                         const float* dX3, const float* dX4, long dx_stride_k, const float* e1w, const float* e1b,
+                         const float* e2w, float* partial, int n_blocks, hipStream_t stream) {
+  if ((long)K * N * T * W == 0) return 0;
+  TOUED_REQUIRE(snap_ph && snap_last, "toued_embed_bwd_snap: the snapshots are required");
+  TOUED_REQUIRE((long)K * N * (T + 1) * W < (1L << 31), "toued_embed_bwd_snap: K*N*(T+1)*W = %ld samples exceed 2^31",
+                (long)K * N * (T + 1) * W);
+#define L_(KER) hipLaunchKernelGGL(KER, dim3(n_blocks), dim3(256), 0, stream, N, W, T, D, K, snap_ph, 0L, 0,          \
+                                   (const int*)nullptr, tidx_stride, ttime_hist, tdone_hist, tstep_stride, dX3, dX4, \
+                                   dx_stride_k, e1w, e1b, e2w, partial, snap_last)
+  if (W % 64 == 0) L_((k_embed_bwd3<true, true>)); else L_((k_embed_bwd3<false, true>));
 #undef L_
   TOUED_CHECK_LAUNCH();
   return 0;

@@ -103,6 +103,9 @@ _SIGS = {
     "toued_sum_rows_add": [_P, _I, _I, _P, _P],
     "toued_sample_random_keys": [_P, _I, _I, _I, _P, _P, _P, _U, _P, _P, _P],
     "toued_entropy_clip_hvp": [_I] * 5 + [_P] * 9 + [_F] * 2 + [_P] * 5 + [_F] * 3 + [_P] + [_F] * 3 + [_P] * 3,
+    "toued_agent_step_snap": [_I, _I, _I, _I] + [_P] * 9 + [_F] * 4 + [_P] * 13,
+    "toued_entropy_clip_hvp_snap": [_I] * 5 + [_P] * 11 + [_F] * 2 + [_P] * 5 + [_F] * 3 + [_P] + [_F] * 3 + [_P] * 3,
+    "toued_embed_bwd_snap": [_I] * 5 + [_P, _P, _P, _L, _P, _L, _P, _P, _L, _P, _P, _P, _P, _I, _P],
     "toued_meta_metrics": [_I, _I, _P, _F, _P, _F, _F, _F, _F, _P, _P],
     "toued_entropy_clip": [_I, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P],
     "toued_a2c_chain_fits": [_I, _I, _I],

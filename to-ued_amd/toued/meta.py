@@ -164,18 +164,17 @@ class MetaGradStep:
         self.R = R
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
         z = lambda *s, dt=f32: torch.zeros(s, dtype=dt, device=dev)
-        # parameter history theta_0 .. theta_K as a ring of K + 1 slots: a step keeps theta_k in slot (r + k) % (K + 1),
-        # r = self._ring; the agents' own tables are bound to slot r (theta_0) and after the step to slot r + K
-        # (theta_K), which is the next step's theta_0 -- no copy back into a fixed slot
-        self._theta_store = z(K + 1, N, D, 5)
-        self._phi_store = z(K + 1, N, D, Y)
+        # the dense parameter history theta_0 .. theta_K of the ring path (self.hist_sparse False, below): a ring of
+        # K + 1 slots, a step keeps theta_k in slot (r + k) % (K + 1), r = self._ring; the agents' own tables are bound
+        # to slot r (theta_0) and after the step to slot r + K (theta_K), which is the next step's theta_0 -- no copy
+        # back into a fixed slot
         self._ring = 0        # this step's slot of theta_0
         self._ring_last = 0   # the last step's (theta_h / phi_h below)
         self.G_th = z(K, N, D, 5)
         self.G_ph = z(K, N, D, Y)
-        # inner updates as toued_agent_step (sparse: theta_{k+1} copied on a side stream beside rollout k and the
-        # LPG forward, then only the touched rows rewritten; the touched gradient rows kept for the reverse pass's
-        # toued_entropy_clip / toued_hvp) where one agent's samples fit the sorted row kernel;
+        # inner updates as toued_agent_step (row-sparse; on the ring path theta_{k+1} is copied on a side stream beside
+        # rollout k and the LPG forward, then only the touched rows rewritten; the touched gradient rows kept for the
+        # reverse pass's toued_entropy_clip / toued_hvp) where one agent's samples fit the sorted row kernel;
         # TOUED_META_FUSED_STEP=0 keeps the dense grad + apply + entropy + clip_dot path
         self.fused_step = (os.environ.get("TOUED_META_FUSED_STEP", "1") != "0"
                            and bool(_lib.lib().toued_agent_update_fits(W, T, D)))
@@ -185,6 +184,24 @@ class MetaGradStep:
         # the reverse pass's entropy-clip and HVP of step k in one launch (toued_entropy_clip_hvp);
         # TOUED_REVERSE_PAIR=0: two launches (bit-identical)
         self.reverse_pair = os.environ.get("TOUED_REVERSE_PAIR", "1") != "0"
+        # sparse history (default): the agents' tables are the one live pair, updated in place by
+        # toued_agent_step_snap, which leaves the reverse pass the rows it reads of theta_k / phi_k (snap_*0) and
+        # theta_{k+1} / phi_{k+1} (snap_*1) at rollout k's samples, contiguous in sample order, plus the time rows --
+        # no ring, no copies.  TOUED_HIST_SPARSE=0 keeps the ring of K + 1 dense table pairs (bit-identical); the
+        # sparse kernels exist for the one-launch update and reverse step only, so the study knobs that split those
+        # launches run on the ring too, as does TOUED_HIST_RING=0 (a request for the dense history in fixed slots).
+        self.hist_sparse = (os.environ.get("TOUED_HIST_SPARSE", "1") != "0" and self.fused_step
+                            and self.step_entropy and self.reverse_pair
+                            and os.environ.get("TOUED_HIST_RING", "1") != "0")
+        if self.hist_sparse:
+            self._theta_store = self._phi_store = None
+            self.snap_th0, self.snap_th1 = z(K, N, T * W, 5), z(K, N, T * W, 5)
+            self.snap_ph0, self.snap_ph1 = z(K, N, (T + 1) * W, Y), z(K, N, T * W, Y)
+            self.snap_last0, self.snap_last1 = z(K, N, 16), z(K, N, 16)
+            self._live = None   # the last chunk's (theta, phi): theta_K of the last step
+        else:
+            self._theta_store = z(K + 1, N, D, 5)
+            self._phi_store = z(K + 1, N, D, Y)
         self.gstat = z(K, N, 4)
         self.met = z(K, N, 8)
         self.traj = Transition(z(K + 1, N, T + 1, W, dt=i32), z(K + 1, N, T + 1, W, dt=i32),
@@ -222,11 +239,35 @@ class MetaGradStep:
     def theta_h(self) -> torch.Tensor:
         """theta_0 .. theta_K of the last step [K + 1, N, D, 5] (copied out of the ring in that order; slot K holds the
         agents' tables, which the level sampler rewrites in place for terminated agents)."""
+        if self.hist_sparse:
+            return self._dense_history(0)
         return torch.roll(self._theta_store, -self._ring_last, dims=0)
 
     @property
     def phi_h(self) -> torch.Tensor:
+        if self.hist_sparse:
+            return self._dense_history(1)
         return torch.roll(self._phi_store, -self._ring_last, dims=0)
+
+    def _dense_history(self, which: int) -> torch.Tensor:
+        """The sparse path's theta_0 .. theta_K (which = 0) or phi_0 .. phi_K (1) as dense tables, for inspection: the
+        step keeps none, so they are rebuilt backwards from the live tables (theta_K) -- update k changed only the
+        rows of rollout k's samples and the time row, whose theta_k values are its snapshots."""
+        if self._live is None:
+            raise RuntimeError("MetaGradStep: no step has run yet")
+        K, T, W, D = self.K, self.T, self.W, self.D
+        live = self._live[which]
+        snap = (self.snap_th0, self.snap_ph0)[which][:, :, :T * W]
+        last = self.snap_last0[:, :, :5] if which == 0 else self.snap_last0[:, :, 8:16]
+        c = live.shape[-1]
+        idx = self.traj.obs_idx[:K, :, :T].reshape(K, self.N, T * W, 1).long().expand(-1, -1, -1, c)
+        out = torch.empty((K + 1,) + tuple(live.shape), dtype=live.dtype, device=live.device)
+        out[K] = live
+        for k in range(K - 1, -1, -1):
+            out[k] = out[k + 1]
+            out[k].scatter_(1, idx[k], snap[k])   # (samples sharing a row carry the same theta_k row)
+            out[k][:, D - 1] = last[k]
+        return out
 
     def _t(self, k: int) -> Transition:
         tr = self.traj
@@ -294,13 +335,23 @@ class MetaGradStep:
         L.call("toued_meta_keys", ptr(agent_keys), N, K, ptr(self.keys_roll), ptr(self.keys_eval),
                ptr(self.keys_ea_reset), ptr(self.keys_ea_roll), st)
         # the history ring's slots in this step's order (theta_k = th[k])
-        bound = self.n_chunks == 1 and isinstance(agents, AgentBatch)
+        sparse = self.hist_sparse
+        bound = not sparse and self.n_chunks == 1 and isinstance(agents, AgentBatch)
         ring = bound and os.environ.get("TOUED_HIST_RING", "1") != "0"
         r0 = self._ring if ring else 0
-        th = [self._theta_store[(r0 + k) % (K + 1)] for k in range(K + 1)]
-        ph = [self._phi_store[(r0 + k) % (K + 1)] for k in range(K + 1)]
+        if sparse:
+            # no history: theta_k is the agents' own table pair (a chunk's: its rows of it) at the time of use
+            th = [agents.theta] * (K + 1)
+            ph = [agents.phi] * (K + 1)
+            self._live = (agents.theta, agents.phi)
+        else:
+            th = [self._theta_store[(r0 + k) % (K + 1)] for k in range(K + 1)]
+            ph = [self._phi_store[(r0 + k) % (K + 1)] for k in range(K + 1)]
         self._ring_last = r0
-        if bound:
+        if sparse:
+            if not (agents.theta.is_contiguous() and agents.phi.is_contiguous()):
+                raise ValueError("MetaGradStep: the agents' tables must be contiguous (they are updated in place)")
+        elif bound:
             # the agents' tables live in the ring (bound at the first step): theta_0 needs no copy, and theta_K's slot
             # becomes the agents' tables (and the next step's theta_0) at the end
             if agents.theta.data_ptr() != th[0].data_ptr():
@@ -344,7 +395,7 @@ class MetaGradStep:
         # ---------------- forward: K inner updates (agents/lpg_agent.py:88-140)
         for k in range(K):
             tk = self._t(k)
-            if self.fused_step:
+            if self.fused_step and not sparse:
                 # theta_{k+1} <- theta_k beside this update's rollout and LPG forward (theta_k is final here)
                 self.side.wait_stream(main)
                 with torch.cuda.stream(self.side):
@@ -374,7 +425,16 @@ class MetaGradStep:
             if nan_checker().enabled:   # the update's saved GRU states h_in [256][T*R] (a column block of the operand)
                 nan_checker().check("lpg_gru_states", self.gru.hin_block(k))
             nan_checker().check("lpg_outputs", self.pi_hat[k], self.y_hat[k])
-            if self.fused_step:
+            if sparse:
+                # the update in place on the live tables, the new policy's entropy metrics and the reverse pass's row
+                # snapshots in one launch
+                L.call("toued_agent_step_snap", N, W, T, D, ptr(th[k]), ptr(ph[k]), ptr(tk.obs_idx), ptr(tk.obs_time),
+                       ptr(tk.action), ptr(tk.reward), ptr(tk.done), ptr(self.pi_hat[k]), ptr(self.y_hat[k]),
+                       hyp.agent_target_coeff, hyp.actor_lr, hyp.critic_lr, hyp.max_grad_norm, ptr(self.G_th[k]),
+                       ptr(self.G_ph[k]), ptr(self.met[k]), ptr(agents.step), ptr(agents.levels), ptr(self.gstat[k]),
+                       ptr(self.snap_th0[k]), ptr(self.snap_ph0[k]), ptr(self.snap_last0[k]), ptr(self.snap_th1[k]),
+                       ptr(self.snap_ph1[k]), ptr(self.snap_last1[k]), st)
+            elif self.fused_step:
                 # the update and the new policy's entropy metrics (toued_entropy's metric mode) in one launch, once
                 # theta_{k+1}'s copy is done (an event: the side stream may hold eval_agent's chain behind it)
                 main.wait_event(copy_done)
@@ -473,6 +533,16 @@ class MetaGradStep:
         for k in range(K - 1, -1, -1):
             tk = self._t(k)
             # d(-b0*H_pi - b1*H_y)/K at (theta_{k+1}, phi_{k+1}) on rollout k, then the clip-VJP coefficients
+            if sparse:
+                # the one-launch reverse step on update k's row snapshots (contiguous reads, no dense theta_k)
+                L.call("toued_entropy_clip_hvp_snap", N, W, T, D, K, ptr(self.snap_th1[k]), ptr(self.snap_ph1[k]),
+                       ptr(self.snap_last1[k]), ptr(self.snap_th0[k]), ptr(self.snap_ph0[k]), ptr(self.snap_last0[k]),
+                       ptr(tk.obs_idx), ptr(tk.obs_time), ptr(tk.action), ptr(self.pi_hat[k]), ptr(self.y_hat[k]),
+                       -hyp.policy_entropy_coeff / K, -hyp.target_entropy_coeff / K, ptr(self.adj_th[a_in]),
+                       ptr(self.adj_ph[a_in]), ptr(self.G_th[k]), ptr(self.G_ph[k]), ptr(self.gstat[k]), hyp.actor_lr,
+                       hyp.critic_lr, hyp.max_grad_norm, ptr(self.coef), hyp.agent_target_coeff, hyp.policy_l2_coeff,
+                       hyp.target_l2_coeff, ptr(self.d_pi_hat[k]), ptr(self.d_y_hat[k]), st)
+                continue
             if self.fused_step and self.reverse_pair:
                 # entropy adjoint + clip coefficients, then the HVP rows, in one launch (one sort of rollout k)
                 L.call("toued_entropy_clip_hvp", N, W, T, D, K, ptr(th[k + 1]), ptr(ph[k + 1]),
@@ -517,9 +587,15 @@ class MetaGradStep:
         if "cum" not in ea:
             raise RuntimeError("MetaGradStep: the GRU backward returned without launching eval_agent")
         tr = self.traj
-        L.call("toued_embed_bwd", N, W, T, D, K, ptr(self._phi_store), self._phi_store[0].numel(), r0, ptr(tr.obs_idx),
-               tr.obs_idx[0].numel(), ptr(tr.obs_time), ptr(tr.done), tr.done[0].numel(), ptr(self.gru.dX3),
-               ptr(self.gru.dX4), T * R, ptr(e1w), ptr(e1b), ptr(e2w), ptr(self.embed_partial), self.embed_blocks, st)
+        if sparse:
+            L.call("toued_embed_bwd_snap", N, W, T, D, K, ptr(self.snap_ph0), ptr(self.snap_last0), ptr(tr.obs_time),
+                   tr.obs_idx[0].numel(), ptr(tr.done), tr.done[0].numel(), ptr(self.gru.dX3), ptr(self.gru.dX4), T * R,
+                   ptr(e1w), ptr(e1b), ptr(e2w), ptr(self.embed_partial), self.embed_blocks, st)
+        else:
+            L.call("toued_embed_bwd", N, W, T, D, K, ptr(self._phi_store), self._phi_store[0].numel(), r0,
+                   ptr(tr.obs_idx), tr.obs_idx[0].numel(), ptr(tr.obs_time), ptr(tr.done), tr.done[0].numel(),
+                   ptr(self.gru.dX3), ptr(self.gru.dX4), T * R, ptr(e1w), ptr(e1b), ptr(e2w), ptr(self.embed_partial),
+                   self.embed_blocks, st)
         # e1_b, e1_w, e2_b, e2_w are contiguous in eta in the partials' order: the block sums added in one launch
         o = self.lay.offsets["e1_b"]
         assert self.lay.offsets["e2_w"] + 16 == o + 161
@@ -530,7 +606,9 @@ class MetaGradStep:
         ea_cum.record_stream(main)
         ea["state"].record_stream(main)
         nan_checker().check("eval_returns", ea_cum)
-        if ring:
+        if sparse:
+            pass   # the agents' tables were updated in place
+        elif ring:
             agents.theta = th[K]
             agents.phi = ph[K]
             self._ring = (r0 + K) % (K + 1)
@@ -668,10 +746,12 @@ def make_lpg_train_step(args, level_sampler, n_agents: int | None = None, world=
     ``(lpg_train_state, agent_states, value_critic_states, metrics)``.
 
     agent_states: agents.AgentBatch of this rank's agents (``rank_slice`` = (lo, hi, n_total) under data
-    parallelism; n_agents defaults to its size).  The meta-gradient step binds ``agent_states.theta`` / ``.phi`` to
-    slots of its parameter-history ring (copying the tables once at the first call) and rebinds them to theta_K's
-    slot at the end of every call (no copy back), so the returned states are the inputs with updated attributes; a
-    tensor reference taken to the tables before a call is not updated by it.  value_critic_states: ValueCriticStates or None (then the ones
+    parallelism; n_agents defaults to its size).  The meta-gradient step updates ``agent_states.theta`` / ``.phi``
+    in place (they are the one live table pair; the reverse pass reads per-update row snapshots).  With
+    TOUED_HIST_SPARSE=0 it instead binds them to slots of its parameter-history ring (copying the tables once at the
+    first call) and rebinds them to theta_K's slot at the end of every call (no copy back), so the returned states
+    are the inputs with updated attributes, and a tensor reference taken to the tables before a call is not updated
+    by it.  value_critic_states: ValueCriticStates or None (then the ones
     inside agent_states are used); ignored by the ES step, as in the reference.  ``impl``: an already built
     MetaGradStep / ESTrainStep to drive (train.Trainer keeps its instance for timers and buffers)."""
     n_local = n_agents if n_agents is not None else (args.num_agents if rank_slice is None

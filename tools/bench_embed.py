@@ -42,6 +42,11 @@ def main():
         part = torch.zeros(nb, 161, device="cuda")
 
         def run():
+            if s.hist_sparse:   # the default step keeps row snapshots, not dense phi_k (TOUED_HIST_SPARSE=0: the ring)
+                L.call("toued_embed_bwd_snap", N, W, T, D, K, L.ptr(s.snap_ph0), L.ptr(s.snap_last0),
+                       L.ptr(t.obs_time), t.obs_idx[0].numel(), L.ptr(t.done), t.done[0].numel(), L.ptr(s.gru.dX3),
+                       L.ptr(s.gru.dX4), T * R, L.ptr(e1w), L.ptr(e1b), L.ptr(e2w), L.ptr(part), nb, L.stream_ptr())
+                return
             L.call("toued_embed_bwd", N, W, T, D, K, L.ptr(s._phi_store), s._phi_store[0].numel(), s._ring_last,
                    L.ptr(t.obs_idx),
                    t.obs_idx[0].numel(), L.ptr(t.obs_time), L.ptr(t.done), t.done[0].numel(), L.ptr(s.gru.dX3),
