@@ -215,6 +215,24 @@ int toued_plr_parent_ids(int B, int N, const float* score, const uint8_t* fresh,
 int toued_plr_sample(int B, int N, const float* score, const uint8_t* active, const uint8_t* fresh,
                      const uint32_t* keys, int proportional, float temperature, float p_replay, int* chosen, int* rep,
                      int* rnd, int* use_out, hipStream_t stream);
+/* The same round with PLR's replay distribution (Jiang et al. 2021, section 3; not in the reference).  transform: 0
+ * rank (top-N), 1 proportional, 2 rank_sampled.  With valid = !fresh && !active, all in f32, correctly rounded:
+ *   score part   ps = w / seq_sum(w); w = valid ? pexp(score / T) : 0 for transforms 0 and 1 (toued_plr_sample's), and
+ *                w = valid ? pexp(-plog(rank) / T) : 0 for 2, rank = 1 + position in the stable jax-order argsort of
+ *                where(valid, -score, +inf);
+ *   staleness    (staleness_coeff > 0 only) a = valid ? max(now - stamp, 0) : 0, A = sum(a) in 64-bit integers,
+ *                pc = A > 0 ? a / A : (valid ? 1 / n_valid : 0);
+ *   mixture      p = (1 - coeff) * ps + coeff * pc, or ps when coeff == 0 (stamp is not read and may be null);
+ *   floor        for transform 2 or coeff > 0: p = valid ? (p < FLT_MIN ? FLT_MIN : p) : 0, which keeps every valid
+ *                slot's Gumbel key finite, ahead of the invalid slots' +inf.
+ * With fewer than N valid slots p = 1 everywhere and use = 0, as in toued_plr_sample.  Replay ids:
+ * flip(argsort(p))[:N] for transform 0, else the Gumbel top-k of toued_plr_sample.  stamp[B]: the round each slot was
+ * last scored or reset in.  p_out[B] (may be null) receives p.  Transforms 0 and 1 with staleness_coeff == 0 give
+ * toued_plr_sample's outputs.  One workgroup, B <= 8192, 0 <= staleness_coeff <= 1. */
+int toued_plr_sample_prio(int B, int N, const float* score, const uint8_t* active, const uint8_t* fresh,
+                          const int* stamp, int now, const uint32_t* keys, int transform, float temperature,
+                          float staleness_coeff, float p_replay, int* chosen, int* rep, int* rnd, int* use_out,
+                          float* p_out, hipStream_t stream);
 
 /* ---- Agents (agents/agents.py:31-95; models/agent.py:7-45) ---- */
 /* Dense(cols, use_bias=False) lecun_normal kernels [n][D][cols]: truncated_normal(keys[i]) in

@@ -129,6 +129,7 @@ _SIGS = {
     "toued_plr_reset_ids": [_I, _I, _P, _P, _P, _P, _P],
     "toued_plr_parent_ids": [_I, _I, _P, _P, _P, _P, _P],
     "toued_plr_sample": [_I, _I, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P],
+    "toued_plr_sample_prio": [_I, _I, _P, _P, _P, _P, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P],
     "toued_wgrad_workspace_floats": [_I, _I, _L],
     "toued_wgrad": [_I, _I, _L, _P, _L, _P, _L, _P, _P, ctypes.c_size_t, _P],
     "toued_wgrad_ldc": [_I, _I, _L, _P, _L, _P, _L, _P, _I, _P, ctypes.c_size_t, _P],

@@ -21,7 +21,8 @@ unpinned, no reference checkpoint exists to read back:
 ``level_buffer_state_dict`` writes the reference's ``LevelBuffer`` pytree (level_sampler.py:30-52): ``level``
 = ``Level(env_params, lifetime, buffer_id)`` (util/data.py:46-51) with every ``EnvParams`` field
 (gridworld.py:21-35, per-type object tables included: the packed rows carry them), then ``score``, ``active``,
-``new`` -- in dataclass field order, as flax's to_state_dict emits them.  ``es_train_state_dict`` writes
+``new`` -- in dataclass field order, as flax's to_state_dict emits them; a buffer with stamps (--staleness_coeff > 0,
+not in the reference) appends ``stamp`` (int32 [B]) and ``clock`` (int32 scalar).  ``es_train_state_dict`` writes
 ``ESTrainState`` (util/data.py:63-68): ``train_state`` (the LPG TrainState, which the ES step never updates),
 ``es_params`` and ``es_state`` of evosax 0.1.4's OpenES (EvoParams / EvoState with the optimiser's
 OptParams / OptState; evosax is not installed or vendored: field names, order and defaults restated, unpinned).
@@ -181,10 +182,14 @@ def level_buffer_state_dict(buffer, spec) -> dict:
     """to_state_dict(LevelBuffer) of the reference (level_sampler.py:30-52) from the packed device buffer."""
     from .env import unpack_levels
     params, lifetime, buffer_id = unpack_levels(buffer.levels, spec)
-    return {"level": {"env_params": params, "lifetime": lifetime.astype(np.int32), "buffer_id": buffer_id.astype(np.int32)},
-            "score": buffer.score.detach().cpu().numpy().astype(np.float32),
-            "active": buffer.active.detach().cpu().numpy().astype(bool),
-            "new": buffer.new.detach().cpu().numpy().astype(bool)}
+    state = {"level": {"env_params": params, "lifetime": lifetime.astype(np.int32), "buffer_id": buffer_id.astype(np.int32)},
+             "score": buffer.score.detach().cpu().numpy().astype(np.float32),
+             "active": buffer.active.detach().cpu().numpy().astype(bool),
+             "new": buffer.new.detach().cpu().numpy().astype(bool)}
+    if getattr(buffer, "stamp", None) is not None:      # --staleness_coeff > 0 (not in the reference's pytree)
+        state["stamp"] = buffer.stamp.detach().cpu().numpy().astype(np.int32)
+        state["clock"] = np.asarray(buffer.clock, np.int32)
+    return state
 
 
 def level_buffer_from_state_dict(state: dict, spec, device):
@@ -195,8 +200,9 @@ def level_buffer_from_state_dict(state: dict, spec, device):
     packed = pack_levels(lv["env_params"], np.asarray(lv["lifetime"]).astype(np.int32),
                          np.asarray(lv["buffer_id"]).astype(np.int32), spec)
     t = lambda a, dt: torch.as_tensor(np.array(a), dtype=dt, device=device)
+    stamp = t(state["stamp"], torch.int32) if "stamp" in state else None
     return LevelBuffer(t(packed, torch.int32), t(state["score"], torch.float32), t(state["active"], torch.bool),
-                       t(state["new"], torch.bool))
+                       t(state["new"], torch.bool), stamp, int(state.get("clock", 0)))
 
 
 _F32_MAX = float(np.finfo(np.float32).max)

@@ -13,6 +13,11 @@ Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
 level instead of a fresh draw of the generator (toued.plr.reset_lowest_scoring).
+Replay distribution (``--score_transform``, ``--staleness_coeff``): ``rank`` (the N best-scoring slots) and
+``proportional`` (softmax of the score) are the reference's; ``rank_sampled`` (not in the reference) is Prioritized Level
+Replay's rank prioritisation, sampled: weight rank^(-1/score_temperature).  ``--staleness_coeff`` rho > 0 (not in the
+reference) mixes any of the three with PLR's staleness distribution, P = (1 - rho) P_S + rho P_C, P_C proportional to
+the rounds since a slot was last scored (``LevelBuffer.stamp`` / ``clock``; toued.plr.replay_distribution).
 All state is device-resident; per-agent work is
 computed for the whole batch and masked by ``terminated`` exactly like the
 reference's vmapped ``jnp.where`` (the masked-out work has no observable effect).
@@ -33,18 +38,23 @@ from .rollout import RolloutWrapper
 
 SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
-SCORE_TRANSFORMS = ["proportional", "rank"]
+SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
+TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
 LEVEL_EDITORS = ("none", "accel")        # --level_editor: refill reset slots from the generator, or by ACCEL edits
 
 
 @dataclass
 class LevelBuffer:
-    """level_sampler.py:30-52: packed levels [B,64] (buffer_id packed), score, active, new."""
+    """level_sampler.py:30-52: packed levels [B,64] (buffer_id packed), score, active, new.  Not in the reference:
+    ``stamp`` (int32 [B], only with --staleness_coeff > 0), the round each slot was last scored or reset in, and
+    ``clock``, the number of PLR rounds the buffer has been through."""
     levels: torch.Tensor
     score: torch.Tensor
     active: torch.Tensor
     new: torch.Tensor
+    stamp: torch.Tensor | None = None
+    clock: int = 0
 
     def __len__(self):
         return self.score.shape[0]
@@ -109,6 +119,12 @@ class LevelSampler:
         if args.score_transform not in SCORE_TRANSFORMS:
             raise ValueError(
                 f"Level score transform {args.score_transform} not in known transforms: {SCORE_TRANSFORMS}")
+        self.staleness_coeff = float(getattr(args, "staleness_coeff", 0.0))
+        if not 0.0 <= self.staleness_coeff <= 1.0:
+            raise ValueError(f"staleness_coeff {self.staleness_coeff} not in [0, 1]")
+        if self.staleness_coeff > 0.0 and args.score_function in ("random", "frozen"):
+            raise ValueError(f"staleness_coeff > 0 needs a score function that scores buffer slots (got "
+                             f"{args.score_function}, which never scores one)")
         self.score_function = args.score_function
         self.score_transform = args.score_transform
         self.score_temperature = args.score_temperature
@@ -168,8 +184,9 @@ class LevelSampler:
         ids = torch.arange(self.buffer_size, dtype=torch.int32, device=self.dev)
         levels = self.gen(keys, buffer_ids=ids)
         B = self.buffer_size
+        stamp = torch.zeros(B, dtype=torch.int32, device=self.dev) if self.staleness_coeff > 0.0 else None
         return LevelBuffer(levels, torch.zeros(B, device=self.dev), torch.zeros(B, dtype=torch.bool, device=self.dev),
-                           torch.ones(B, dtype=torch.bool, device=self.dev))
+                           torch.ones(B, dtype=torch.bool, device=self.dev), stamp)
 
     def initial_sample(self, rng, level_buffer, batch_size: int, create_value_critics_flag: bool, sl=None):
         """level_sampler.py:103-132.  ``sl`` = (lo, hi, total) agent slice of this rank."""

@@ -21,6 +21,15 @@ expected return of its policy (toued_policy_return) in place of the eval rollout
 deterministic and key-free, and ``alg_regret`` trains its antagonists on the same keys and returns
 V^pi(A2C) - V^pi(LPG).  The default, ``sampled``, is the code path above, bit for bit.
 
+With ``--score_transform rank_sampled`` or ``--staleness_coeff`` > 0 (neither in the reference) step 4 is
+toued_plr_sample_prio: Prioritized Level Replay's replay distribution (Jiang et al. 2021, section 3), the mixture
+(1 - rho) P_S + rho P_C of a score part P_S (rank_sampled: weight rank^(-1/score_temperature) over the descending-score
+ranks, sampled by Gumbel top-k; rank / proportional: the reference's) and a staleness part P_C proportional to the
+rounds since a slot was last scored.  The buffer then carries ``stamp`` (the round of a slot's last score or reset,
+written in steps 1 and 3) and ``clock`` (a host integer, +1 per round); ``sampler.last_plr["p"]`` keeps the
+distribution and ``replay_distribution`` computes it for any buffer.  With the default flags the call is
+toued_plr_sample and no stamp exists.
+
 Multi-GPU: the buffer is replicated on every rank and updated identically; each rank scores
 its own agents and the per-agent (term, score, buffer id) vectors are all-gathered, so every
 rank runs the same single-workgroup sampler kernel on the same inputs.
@@ -40,6 +49,7 @@ from .a2c import A2CHyperparams, A2CTrainer
 from .debug import nan_checker
 from .agents import AgentBatch, create_agents, eval_agent, eval_agent_reset
 from .env import L_BUFID
+from .level_sampler import TRANSFORM_CODES
 from .rollout import Transition
 
 
@@ -62,8 +72,9 @@ def parent_ids(buffer, reset_ids: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int) -> torch.Tensor:
-    """level_sampler.py:331-353, in place on ``buffer``; returns the reset ids [n_new].
+def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: int | None = None) -> torch.Tensor:
+    """level_sampler.py:331-353, in place on ``buffer``; returns the reset ids [n_new].  A buffer with stamps
+    (--staleness_coeff > 0) gets ``stamp[ids] = now``.
 
     With ``--level_editor accel`` (not in the reference) the generated levels then pass through the level editor:
     a row whose coin (``--edit_prob``) says so becomes an edited copy of a parent, a scored buffer level read before
@@ -88,6 +99,8 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int) -> torc
     new.index_fill_(0, il, True)
     buffer.active.index_fill_(0, il, False)
     buffer.new = new
+    if buffer.stamp is not None and now is not None:
+        buffer.stamp.index_fill_(0, il, int(now))
     return ids
 
 
@@ -234,6 +247,32 @@ def _scatter_into(dst: torch.Tensor, ids: torch.Tensor, val) -> None:
     dst.copy_(ext[:-1])
 
 
+def replay_distribution(buffer, n: int, transform: str, temperature: float, staleness_coeff: float = 0.0,
+                        now: int | None = None) -> torch.Tensor:
+    """The distribution p [B] that a round of ``n`` agents would draw its replay levels from (toued_plr_sample_prio's
+    ``p_out``; the ids it draws go to scratch): ``transform`` one of SCORE_TRANSFORMS, ``temperature`` the
+    --score_temperature, ``staleness_coeff`` the --staleness_coeff (needs ``buffer.stamp``), ``now`` the round the
+    staleness is measured at (default: the buffer's next round, ``buffer.clock + 1``).  Not in the reference."""
+    if transform not in TRANSFORM_CODES:
+        raise ValueError(f"Level score transform {transform} not in known transforms: {sorted(TRANSFORM_CODES)}")
+    rho = float(staleness_coeff)
+    if rho > 0.0 and buffer.stamp is None:
+        raise ValueError("staleness_coeff > 0 needs a level buffer with stamps")
+    B = len(buffer)
+    dev = buffer.score.device
+    now = buffer.clock + 1 if now is None else int(now)
+    p = torch.empty(B, dtype=torch.float32, device=dev)
+    if not 1 <= n <= B:
+        raise ValueError(f"replay_distribution: need 1 <= n <= {B} (got {n})")
+    ids = torch.empty((4, n), dtype=torch.int32, device=dev)
+    keys = torch.zeros((3, 2), dtype=torch.int32, device=dev)
+    _lib.call("toued_plr_sample_prio", B, n, _lib.ptr(buffer.score), _lib.ptr(buffer.active), _lib.ptr(buffer.new),
+              _lib.ptr(buffer.stamp if rho > 0.0 else None), now, _lib.ptr(keys), TRANSFORM_CODES[transform],
+              float(temperature), rho, 0.5, _lib.ptr(ids[0]), _lib.ptr(ids[1]), _lib.ptr(ids[2]), _lib.ptr(ids[3]),
+              _lib.ptr(p), _lib.stream_ptr())
+    return p
+
+
 def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: torch.Tensor, sl=None):
     """Returns (rng, buffer, new_levels [n_local, 64]) — new_levels for terminated agents, the
     caller keeps the old level elsewhere (``term_mask_fn``)."""
@@ -257,8 +296,9 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     # dropped them: keep their blocks from being reused by main until the side stream's work has passed them
     sub.record_stream(side)
     buffer.new.record_stream(side)
+    now = buffer.clock + 1      # this round's number: a host integer, no device read
     with torch.cuda.stream(side):
-        reset_lowest_scoring(sampler, sub, buffer, N)
+        reset_lowest_scoring(sampler, sub, buffer, N, now)
     rng, sub = _split2(rng)
     keys = prng.split(sub, N)
     if sl is not None:
@@ -294,16 +334,32 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     _scatter_into(buffer.score, t_ids, score_g)
     _scatter_into(buffer.active, t_ids, False)
     _scatter_into(buffer.new, t_ids, False)
+    if buffer.stamp is not None:       # the gathered ids: every rank's copy stays identical
+        _scatter_into(buffer.stamp, t_ids, now)
     # replay vs random (:203-227)
     ks = prng.split(rng, 3)                           # rng, replay_rng, random_rng
     kbuf = torch.stack([ks[1], ks[2], ks[0]]).contiguous()
     chosen = torch.empty(N, dtype=torch.int32, device=dev)
     rep, rnd, use = torch.empty_like(chosen), torch.empty_like(chosen), torch.empty_like(chosen)
-    _lib.call("toued_plr_sample", B, N, _lib.ptr(buffer.score), _lib.ptr(buffer.active), _lib.ptr(buffer.new),
-              _lib.ptr(kbuf), int(sampler.score_transform == "proportional"), float(sampler.score_temperature),
-              float(sampler.p_replay), _lib.ptr(chosen), _lib.ptr(rep), _lib.ptr(rnd), _lib.ptr(use),
-              _lib.stream_ptr())
+    rho = float(getattr(sampler, "staleness_coeff", 0.0))
     sampler.last_plr = {"replay": rep, "random": rnd, "use": use, "chosen": chosen, "score": score_g}
+    if sampler.score_transform == "rank_sampled" or rho > 0.0:
+        if rho > 0.0 and buffer.stamp is None:
+            raise ValueError("staleness_coeff > 0 needs a level buffer with stamps (LevelSampler.initialize_buffer "
+                             "makes them; a checkpoint written without them has none)")
+        p = torch.empty(B, dtype=torch.float32, device=dev)
+        _lib.call("toued_plr_sample_prio", B, N, _lib.ptr(buffer.score), _lib.ptr(buffer.active),
+                  _lib.ptr(buffer.new), _lib.ptr(buffer.stamp if rho > 0.0 else None), now, _lib.ptr(kbuf),
+                  TRANSFORM_CODES[sampler.score_transform], float(sampler.score_temperature), rho,
+                  float(sampler.p_replay), _lib.ptr(chosen), _lib.ptr(rep), _lib.ptr(rnd), _lib.ptr(use), _lib.ptr(p),
+                  _lib.stream_ptr())
+        sampler.last_plr["p"] = p
+    else:
+        _lib.call("toued_plr_sample", B, N, _lib.ptr(buffer.score), _lib.ptr(buffer.active), _lib.ptr(buffer.new),
+                  _lib.ptr(kbuf), int(sampler.score_transform == "proportional"), float(sampler.score_temperature),
+                  float(sampler.p_replay), _lib.ptr(chosen), _lib.ptr(rep), _lib.ptr(rnd), _lib.ptr(use),
+                  _lib.stream_ptr())
+    buffer.clock = now
     r1, _ = _split2(ks[0].contiguous())               # bernoulli: rng, _rng = split(rng)
     rng, _ = _split2(r1)                              # permutation: rng, _rng = split(rng)
     new_ids = torch.where(term_g, chosen, old_g)

@@ -68,7 +68,8 @@ class Trainer:
         if self.buffer is not None and getattr(args, "ref_quirk_checkpoint_init", False):
             from .level_sampler import LevelBuffer
             b = self.buffer
-            self.buffer_init = LevelBuffer(b.levels.clone(), b.score.clone(), b.active.clone(), b.new.clone())
+            self.buffer_init = LevelBuffer(b.levels.clone(), b.score.clone(), b.active.clone(), b.new.clone(),
+                                           None if b.stamp is None else b.stamp.clone(), b.clock)
         if args.use_es:
             from .es import ESTrainStep
             self.step_fn = ESTrainStep(args, self.sampler, n_local, self.eta, self.dev, self.world)
