@@ -193,6 +193,22 @@ int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int 
  * [0, TOUED_MAX_OBJS] or a table over the LDS budget; n == 0 and max_rollout_len == 0 succeed (v0 = 0). */
 int toued_policy_return(const int* levels, const float* theta, int n, int D, int max_grid, int n_max, int tabular,
                         int max_rollout_len, float* v0, float* v_all, hipStream_t stream);
+/* Mean and variance of the first-episode return of n tabular agents' own policies on their levels
+ * (RolloutWrapper.policy_return_moments): toued_policy_return's recursion with a second table,
+ * u_t(s) = Var[G_t | s] = sum_a pi_t(a|s) m2_t(s, a) - v_t(s)^2 with the second moment
+ * m2_t(s, a) = r^2 + c * (2 r E[v_{t+1}] + E[u_{t+1} + v_{t+1}^2]), c = 1 - p_term(s, a) (the law of total variance;
+ * nothing is clipped, neither c < 0 nor a variance that rounds below zero).  The variance is over everything an eval
+ * rollout draws: the policy's actions and the level's termination and respawn draws.  Arguments as
+ * toued_policy_return's; v0, var0 [n] (both required) = v_0 and u_0 at the start state; v_all, var_all (nullable,
+ * independently) [n][max_rollout_len][S], with -inf at the invalid states and zero rows for
+ * t >= max_steps_in_episode in both.  v0 and v_all are bit-identical to toued_policy_return's.  The u tables are held
+ * as f32 in LDS (the step's arithmetic is f64): |var - f64| <= H * 2^-23 * max(1, max|u|), H = min(max_steps,
+ * max_rollout_len).  One launch, no atomics, run-to-run bit-identical; level i's result depends on levels[i] and
+ * theta[i] only.  Errors (-1) as toued_policy_return's, with a lower limit on the table size: the two f32 tables
+ * come on top of its LDS (every tabular mode fits).  n == 0 and max_rollout_len == 0 succeed (v0 = var0 = 0). */
+int toued_policy_return_moments(const int* levels, const float* theta, int n, int D, int max_grid, int n_max,
+                                int tabular, int max_rollout_len, float* v0, float* var0, float* v_all,
+                                float* var_all, hipStream_t stream);
 
 
 /* ---- Level sampler (environments/level_sampler.py) ---- */

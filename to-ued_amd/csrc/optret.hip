@@ -26,7 +26,8 @@
 //     max_rollout_len) backups give v_0, and the rows t >= max_steps of v_all are zero fills.
 //
 // k_policy_return (further down) is the same recursion for the expected return of a tabular agent's own policy,
-// v_t(s) = sum_a pi_t(a|s) q(s, a), on the same setup (optret_setup).
+// v_t(s) = sum_a pi_t(a|s) q(s, a), on the same setup (optret_setup).  k_policy_moments (after it) adds the variance
+// of that return, u_t(s) = Var[G_t | s], in two f32 tables behind the setup's LDS.
 #include "env_dev.h"
 
 namespace {
@@ -369,6 +370,187 @@ int launch_policy_return(int n, int block, size_t lds, hipStream_t stream, const
   return 0;
 }
 
+// dynamic LDS of k_policy_moments: optret_setup's layout (a multiple of 16 bytes), then f32 ua[S], ub[S]
+__host__ __device__ inline size_t polmom_lds_bytes(int G2, int n_max) {
+  return optret_lds_bytes(G2, n_max) + 2 * ((size_t)G2 << n_max) * sizeof(float);
+}
+
+// policy_backup with the return's variance beside its mean: v_t(pos, e) into table `curo` of va by policy_backup's
+// arithmetic, operation for operation, and u_t(pos, e) = Var[G_t | s] into table `curo` of ua.  With v', u' the
+// next state's mean and variance, the second moment of r + cont * G' given (s, a) is
+//   m2(s, a) = r^2 + c * (2 r E[v'] + E[u' + v'^2]),   c = 1 - p_term,
+// and u_t(s) = sum_a pi(a) m2(s, a) - v_t(s)^2 (the law of total variance, nothing clipped: c < 0 is taken as the
+// mean takes it).  u' is read as f32 and everything else is f64; per outcome one more LDS read, u' + v'^2 and one
+// more accumulation than the mean's.
+__device__ __forceinline__ void moments_backup(const OptretSetup& T, float* ua, int nxo, int curo, int pos, int e,
+                                               const float* l) {
+  double* const va = T.va;
+  const double* pw = T.pw;
+  const int G2 = T.G2, NE = T.NE;
+  const int absent = T.used & ~e;
+  const double* pwa = pw + absent * NE;
+  int base[5], col[5];
+  double ev[5], ez[5];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const uint32_t en = T.nxt[pos * 5 + a];
+    col[a] = (int)(en >> 8) & e;
+    base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~col[a]);
+    ev[a] = 0.0;
+    ez[a] = 0.0;
+  }
+  int R0 = 0;
+  do {
+    const int R1 = (R0 - absent) & absent;
+    const double p0 = pwa[R0];
+    const double p1 = pw[R1 != 0 ? absent * NE + R1 : NE * NE];   // pw[NE * NE] = 0
+    const int o0 = G2 * R0, o1 = G2 * R1;
+    double x0[5], x1[5];
+    float y0[5], y1[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+      x0[a] = va[base[a] + o0];
+      x1[a] = va[base[a] + o1];
+      y0[a] = ua[base[a] + o0];
+      y1[a] = ua[base[a] + o1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+      ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
+      const double z0 = __builtin_fma(x0[a], x0[a], (double)y0[a]);
+      const double z1 = __builtin_fma(x1[a], x1[a], (double)y1[a]);
+      ez[a] = __builtin_fma(p1, z1, __builtin_fma(p0, z0, ez[a]));
+    }
+    R0 = R1 != 0 ? (R1 - absent) & absent : 0;
+  } while (R0 != 0);
+  float m = l[0];
+#pragma unroll
+  for (int a = 1; a < 5; ++a) m = fmaxf(m, l[a]);
+  double num = 0.0, den = 0.0, num2 = 0.0;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const double x = exp((double)l[a] - (double)m);
+    const double r = T.rsum[col[a]], keep = T.keepw[col[a]];
+    const double q = r + ev[a] * keep;
+    den += x;
+    num = __builtin_fma(x, q, num);
+    const double m2 = __builtin_fma(keep, __builtin_fma(r + r, ev[a], ez[a]), r * r);
+    num2 = __builtin_fma(x, m2, num2);
+  }
+  const double v = num / den;
+  va[curo + pos + G2 * e] = v;
+  ua[curo + pos + G2 * e] = (float)(num2 / den - v * v);
+}
+
+// Mean and variance of the first-episode return of a tabular agent's own policy: k_policy_return (its setup, work
+// order, block size and mean arithmetic: v0 and v_all are bit-identical to its) with a second table pair for
+// u_t(s) = Var[G_t | s], see moments_backup.  The u tables are f32, double-buffered in LDS behind optret_setup's
+// layout (two more f64 tables would not fit the largest mode), indexed like va; every step's arithmetic is f64 and
+// the f32 store of u_t is the step's only rounding that the f64 recursion does not have.  Invalid states hold -inf in
+// both u tables, as in va, and are never read by a valid state's backup.  A table that fits the LDS with the u tables
+// has at most six items per thread, so there is no MORE.
+template <int ITEMS>
+__global__ __launch_bounds__(1024) void k_policy_moments(const int* __restrict__ levels,
+                                                         const float* __restrict__ theta, int D, int max_grid,
+                                                         int n_max, int L, float* __restrict__ v0,
+                                                         float* __restrict__ var0, float* __restrict__ v_all,
+                                                         float* __restrict__ var_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+  const double* va = T.va;
+  const int G2 = T.G2, S = T.S, H = T.H;
+  float* const ua = reinterpret_cast<float*>(smem + optret_lds_bytes(G2, n_max));
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int ncell = T.ncell;
+  const int nwork = ncell * T.ne;      // <= S <= ITEMS * blockDim (the host's choice of ITEMS)
+
+  // both u tables: u_H = 0 at the valid states, -inf at the invalid ones (va's fill); zero rows of var_all
+  for (int s = tid; s < S; s += nt) ua[s] = ua[S + s] = (float)va[s];
+  if (var_all != nullptr) {
+    float* rows = var_all + ((size_t)blockIdx.x * L + H) * S;
+    const size_t nz = (size_t)(L - H) * S;
+    for (size_t i = tid; i < nz; i += nt) rows[i] = 0.0f;
+  }
+
+  const float* th = theta + (size_t)blockIdx.x * D * 5;
+  float last[5];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) last[a] = th[(size_t)(D - 1) * 5 + a];
+  int st[ITEMS];          // pos | e << 8 of the thread's item k, -1 past the level's work
+  float row[ITEMS][5];
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) {
+    const int w = tid + k * nt;
+    st[k] = -1;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) row[k][a] = 0.0f;
+    if (w < nwork) {
+      const int ei = w / ncell;
+      const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
+      st[k] = pos | (e << 8);
+      const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
+#pragma unroll
+      for (int a = 0; a < 5; ++a) row[k][a] = r[a];
+    }
+  }
+  __syncthreads();
+
+  int curo = 0;    // v_t and u_t, written
+  int nxo = S;     // v_{t+1} and u_{t+1}, read
+  for (int t = H - 1; t >= 0; --t) {
+    const float c = __fmul_rn((float)t, 0.001f);
+    float tl[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) tl[a] = __fmul_rn(c, last[a]);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      if (st[k] < 0) continue;
+      // the item is made opaque per step: what derives from it (next cells, table offsets) is then formed here, not
+      // hoisted out of the time loop for all ITEMS items at once (ITEMS = 4 and 6 spilled to scratch that way)
+      int sk = st[k];
+      asm volatile("" : "+v"(sk));
+      const int pos = sk & 0xFF, e = sk >> 8;
+      float l[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
+      moments_backup(T, ua, nxo, curo, pos, e, l);
+    }
+    lds_barrier();
+    if (v_all != nullptr) {
+      float* out = v_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) out[s] = (float)va[curo + s];
+    }
+    if (var_all != nullptr) {
+      float* out = var_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) out[s] = ua[curo + s];
+    }
+    const int sw = curo; curo = nxo; nxo = sw;
+  }
+  if (tid == 0) {
+    const int si = nxo + T.lev[L_START] + G2 * T.used;
+    v0[blockIdx.x] = H > 0 ? (float)va[si] : 0.0f;
+    var0[blockIdx.x] = H > 0 ? ua[si] : 0.0f;
+  }
+}
+
+template <int ITEMS>
+int launch_policy_moments(int n, int block, size_t lds, hipStream_t stream, const int* levels, const float* theta,
+                          int D, int max_grid, int n_max, int L, float* v0, float* var0, float* v_all,
+                          float* var_all) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_moments<ITEMS>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
+                  "toued_policy_return_moments: cannot raise the dynamic LDS limit");
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((k_policy_moments<ITEMS>), dim3(n), dim3(block), lds, stream, levels, theta, D, max_grid, n_max,
+                     L, v0, var0, v_all, var_all);
+  TOUED_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -431,6 +613,41 @@ int toued_policy_return(const int* levels, const float* theta, int n, int D, int
   if (items <= 6) return TOUED_POLRET_LAUNCH(6, false);      // every mode's table
   return TOUED_POLRET_LAUNCH(4, true);
 #undef TOUED_POLRET_LAUNCH
+}
+
+int toued_policy_return_moments(const int* levels, const float* theta, int n, int D, int max_grid, int n_max,
+                                int tabular, int max_rollout_len, float* v0, float* var0, float* v_all,
+                                float* var_all, hipStream_t stream) {
+  TOUED_REQUIRE(tabular != 0, "toued_policy_return_moments: non-tabular environments are unsupported (the agent is "
+                "not a table over the environment's states)");
+  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_policy_return_moments: n=%d max_rollout_len=%d must be >= 0",
+                n, max_rollout_len);
+  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_policy_return_moments: max_grid=%d outside [1, 16]",
+                max_grid);
+  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_policy_return_moments: n_max=%d outside [0, %d]", n_max,
+                TOUED_MAX_OBJS);
+  const int G2 = max_grid * max_grid;
+  const int S = G2 << n_max;
+  TOUED_REQUIRE(D == S + 1, "toued_policy_return_moments: D=%d is not max_grid^2 * 2^n_max + 1 = %d", D, S + 1);
+  // the f32 variance tables come on top of toued_policy_return's LDS: the limit on the table size is lower here
+  const size_t lds = polmom_lds_bytes(G2, n_max);
+  TOUED_REQUIRE(lds <= kOptretLdsMax,
+                "toued_policy_return_moments: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)", max_grid,
+                n_max, lds, kOptretLdsMax);
+  if (n == 0) return 0;
+  // toued_policy_return's block size and items per thread; a table that fits the LDS has at most six
+  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
+  const int items = (S + block - 1) / block;
+  TOUED_REQUIRE(items <= 6, "toued_policy_return_moments: max_grid=%d n_max=%d has %d states per thread (limit 6)",
+                max_grid, n_max, items);
+#define TOUED_POLMOM_LAUNCH(I)                                                                                     \
+  launch_policy_moments<I>(n, block, lds, stream, levels, theta, D, max_grid, n_max, max_rollout_len, v0, var0, \
+                           v_all, var_all)
+  if (items <= 1) return TOUED_POLMOM_LAUNCH(1);
+  if (items <= 2) return TOUED_POLMOM_LAUNCH(2);
+  if (items <= 4) return TOUED_POLMOM_LAUNCH(4);
+  return TOUED_POLMOM_LAUNCH(6);
+#undef TOUED_POLMOM_LAUNCH
 }
 
 }  // extern "C"

@@ -6,9 +6,11 @@ Score functions: ``random`` (domain randomisation), ``frozen`` (uniform replay
 of a fixed buffer), ``alg_regret`` (PLR with the A2C antagonist's
 algorithmic regret, GROOVE), ``positive_value_loss`` / ``l1_value_loss`` (PLR
 with the mean of max(GAE, 0) / |GAE| of the agent's eval trajectory under its
-value critic; not with --use_es, not in the reference) and ``optimal_regret``
+value critic; not with --use_es, not in the reference), ``optimal_regret``
 (PLR with the true regret against the level's exact optimal return; tabular
-modes, not in the reference).
+modes, not in the reference) and ``return_variance`` (PLR with the exact
+variance of the agent's first-episode return on the level, a learnability
+score; tabular modes, also with --use_es, not in the reference).
 Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
@@ -38,6 +40,7 @@ from .rollout import RolloutWrapper
 
 SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
+MOMENT_SCORE_FUNCTIONS = ("return_variance",)   # accepted beside SCORE_FUNCTIONS: toued.plr.MOMENT_FUNCTIONS
 SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
 TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
@@ -90,6 +93,9 @@ class LevelSampler:
         if args.score_function == "optimal_regret" and not self.spec.tabular:
             raise ValueError(f"Level score function optimal_regret needs a tabular environment mode: the optimal "
                              f"return is not defined for {self.env_mode}")
+        if args.score_function in MOMENT_SCORE_FUNCTIONS and not self.spec.tabular:
+            raise ValueError(f"Level score function {args.score_function} needs a tabular environment mode: the "
+                             f"agent is not a table over the states of {self.env_mode}")
         if args.score_function in VALUE_LOSS_FUNCTIONS and args.use_es:
             raise ValueError(f"Level score function {args.score_function} needs the agents' value critics, which "
                              f"--use_es does not train")
@@ -114,8 +120,9 @@ class LevelSampler:
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
-        if args.score_function not in SCORE_FUNCTIONS:
-            raise ValueError(f"Level score function {args.score_function} not in known functions: {SCORE_FUNCTIONS}")
+        if args.score_function not in SCORE_FUNCTIONS and args.score_function not in MOMENT_SCORE_FUNCTIONS:
+            raise ValueError(f"Level score function {args.score_function} not in known functions: "
+                             f"{SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS)}")
         if args.score_transform not in SCORE_TRANSFORMS:
             raise ValueError(
                 f"Level score transform {args.score_transform} not in known transforms: {SCORE_TRANSFORMS}")

@@ -9,6 +9,11 @@ Additions (all default to the reference's behaviour):
   --regret_eval {sampled,exact}  how alg_regret / optimal_regret evaluate an agent: ``sampled`` (the default) by the
                         reference's eval rollouts, ``exact`` by the exact expected return of the agent's own policy
                         (RolloutWrapper.policy_return; tabular modes)
+  --score_function return_variance  PLR with the exact variance of the agent's first-episode return on its level
+                        (RolloutWrapper.policy_return_moments), the learnability score p (1 - p) of "Sampling for
+                        Learnability" (Rutherford et al. 2024) for real-valued returns: no antagonist, no value critic
+                        (so also with --use_es), no keys, no eval rollout; tabular modes.  The variance includes the
+                        level's own randomness (termination and respawn draws), not only the policy's
   --level_editor {none,accel}  how the PLR scores' reset round refills a freed buffer slot: ``none`` (the default) by
                         the level generator, ``accel`` with probability --edit_prob by --num_edits small edits
                         (--edit_ops: walls, objects, start, rewards; a reward moves by at most --edit_reward_delta) of a
@@ -85,7 +90,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--score_function", help="UED level scoring function (random, frozen, alg_regret, "
                    "positive_value_loss or l1_value_loss: the mean of max(GAE, 0) or |GAE| under the agent's value "
                    "critic, not with --use_es; or optimal_regret: the true regret against the level's exact optimal "
-                   "return, tabular modes; see --regret_eval for the regret scores' agent evaluation)", type=str,
+                   "return, tabular modes; or return_variance: the exact variance of the agent's return on the level, "
+                   "tabular modes; see --regret_eval for the regret scores' agent evaluation)", type=str,
                    default="random")
     p.add_argument("--p_replay", help="Probability of replaying a level from the buffer (vs. random sampling)",
                    type=float, default=0.5)

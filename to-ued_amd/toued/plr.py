@@ -16,6 +16,11 @@ value critic (toued_value_loss_scores), no antagonist; the rest is unchanged.
 With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
 exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
 
+With ``score_function = return_variance`` (tabular modes; not in the reference) step 2 is ``return_variance``: the
+exact variance of the agent's first-episode return on its level (toued_policy_return_moments), the learnability score
+p (1 - p) of "Sampling for Learnability" (Rutherford et al. 2024) for real-valued returns.  One launch: no antagonist,
+no value critic, no keys and no eval rollout.  It is not a regret; the rest is unchanged.
+
 With ``--regret_eval exact`` (tabular modes; not in the reference) the two regret scores evaluate an agent by the exact
 expected return of its policy (toued_policy_return) in place of the eval rollouts: ``optimal_regret`` is V* - V^pi,
 deterministic and key-free, and ``alg_regret`` trains its antagonists on the same keys and returns
@@ -169,6 +174,22 @@ def optimal_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta:
 REGRET_FUNCTIONS = {"alg_regret": algorithmic_regret, "optimal_regret": optimal_regret}
 
 
+def return_variance(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor) -> torch.Tensor:
+    """The exact variance of n LPG agents' first-episode returns on their tabular levels over the eval rollout length
+    (RolloutWrapper.policy_return_moments): zero on a level the agent always or never solves, largest where the
+    outcome is open.  The variance is over the policy's actions and the level's own termination and respawn draws
+    alike.  Same signature and return as ``optimal_regret``; ``keys`` is unused (no rollout, no antagonist, no value
+    critic).  A score, not a regret.  An extension: the reference's LevelSampler has no such score function."""
+    if levels.shape[0] == 0:
+        return torch.zeros(0, device=levels.device)
+    ro = sampler.rollout_manager
+    return ro.policy_return_moments(levels, lpg_theta, ro.eval_rollout_len)[1]
+
+
+# the scores from the moments of the agent's own return: the regret functions' signature
+MOMENT_FUNCTIONS = {"return_variance": return_variance}
+
+
 # value_loss_scores keeps one chunk of agents' eval trajectories at a time (14 bytes per worker and step) under this
 VALUE_LOSS_SCRATCH_BYTES = 1 << 30
 
@@ -308,7 +329,7 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
         vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
         regret = lambda s, k, lv, th, sel=slice(None): value_loss(s, k, lv, th, vcrit[sel].contiguous())
     else:
-        score_fn = REGRET_FUNCTIONS[sampler.score_function]
+        score_fn = REGRET_FUNCTIONS.get(sampler.score_function) or MOMENT_FUNCTIONS[sampler.score_function]
         regret = lambda s, k, lv, th, sel=None: score_fn(s, k, lv, th)
     if sampler.regret_all_agents:
         score = regret(sampler, keys, agents.levels, agents.theta)

@@ -240,6 +240,36 @@ class RolloutWrapper:
                   _lib.ptr(v_all), _lib.stream_ptr())
         return v_all if return_all else v0
 
+    def policy_return_moments(self, levels: torch.Tensor, theta: torch.Tensor, max_rollout_len: int,
+                              return_all: bool = False):
+        """(mean, variance) of the first-episode return of tabular agents' own policies over ``max_rollout_len``
+        steps (toued_policy_return_moments, one launch, no host synchronisation): ``policy_return``'s recursion with a
+        second table for Var[G_t | s], by the law of total variance.  The mean is ``policy_return``'s, bit for bit.
+        The variance is over everything an eval rollout draws, the policy's actions and the level's termination and
+        respawn draws; with ``max_rollout_len = eval_rollout_len`` it is the variance of ``eval_agent``'s per-worker
+        return.  It is not clamped: a zero variance may come out a rounding below zero.  Not in the reference.
+
+        Shapes, the single-agent form and the errors are ``policy_return``'s, for each of the two results."""
+        if not self.spec.tabular:
+            raise NotImplementedError("Policy return moments not implemented for non-tabular environments.")
+        if levels.dim() == 1:
+            m, v = self.policy_return_moments(levels.view(1, -1), theta.unsqueeze(0), max_rollout_len, return_all)
+            return m[0], v[0]
+        n, L = levels.shape[0], int(max_rollout_len)
+        if tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32 \
+                or theta.device != levels.device:
+            raise ValueError(f"policy_return_moments: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, "
+                             f"expected float32 {(n, self.obs_dim, 5)} on {levels.device}")
+        S = self.obs_dim - 1
+        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
+        var0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
+        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
+        var_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
+        _lib.call("toued_policy_return_moments", _lib.ptr(levels), _lib.ptr(theta), n, self.obs_dim,
+                  self.spec.max_grid_size, self.spec.max_n_objs, int(self.spec.tabular), L, _lib.ptr(v0),
+                  _lib.ptr(var0), _lib.ptr(v_all), _lib.ptr(var_all), _lib.stream_ptr())
+        return (v_all, var_all) if return_all else (v0, var0)
+
     def value_loss_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float, gae_lambda: float,
                           return_adv: bool = False):
         """The value-loss PLR scores of N agents' trajectories under their value critics ``vcrit`` f32 [N, D]
