@@ -4,8 +4,9 @@
 Under the switch every GRU launch takes the f32-MFMA kernels: k_gru_fwd<true,2> / k_gru_fwd<false,2> at R % 64 == 0,
 k_gru_bwd<1>, saves in [256][M] rows (n included) and the bf16-triple weight-gradient reduction instead of the
 block-floating-point one.  Runs cases a and c (T = 3) of the forward matrix, heads and saves, one per-candidate run,
-a repeat of case a and of the per-candidate run, and one backward case of tests/test_gpu_meta.py; prints one JSON line of achieved errors and
-bounds, which the parent asserts on.
+a repeat of case a and of the per-candidate run, one backward case of tests/test_gpu_meta.py, and cases a and c (T = 1)
+of the backward matrix (tests/gru_bwd_cases.py, key "bwd_matrix"); prints one JSON line of achieved errors and bounds,
+which the parent asserts on.
 """
 from __future__ import annotations
 
@@ -67,6 +68,14 @@ def main():
     errs, flips = _gru_bwd_case(N, W, T, K, F, eta, xs, done, d_pi, d_y)
     out["bwd"] = {k: float(v) for k, v in errs.items()}
     out["bwd_relu_flips"] = len(flips)
+    # the backward matrix's cases a (4 x 32) and c (T = 1): k_gru_bwd<1> at R % 64 == 0, every output it writes
+    import gru_bwd_cases as bc
+    out["bwd_matrix"], out["bwd_matrix_instance"] = {}, {}
+    for tag in ("a", "c-T1"):
+        res, run, got, _ = bc.run_case(tag)
+        assert {"dn_pre", "relu_out", "dh_heads"} <= set(got) and "col_exp" not in got
+        out["bwd_matrix"][tag] = res
+        out["bwd_matrix_instance"][tag] = bc.instance(run.gru)
     print(json.dumps(out), flush=True)
 
 

@@ -366,7 +366,8 @@ def test_f32_fallback_process():
     """The documented fallback switch TOUED_GRU_F32=1 (read once per process: a fresh child, tests/gru_f32_worker.py):
     k_gru_fwd<true,2> on cases a and c (T = 3), heads and the five saves, and its repeat; k_gru_fwd<false,2> on two
     candidates; k_gru_bwd<1> at R % 64 == 0 with the non-block-floating-point weight-gradient reduction on one
-    _gru_bwd_case of tests/test_gpu_meta.py at that file's f32 bound of 1e-4."""
+    _gru_bwd_case of tests/test_gpu_meta.py at that file's f32 bound of 1e-4, and on cases a and c (T = 1) of the
+    backward matrix (tests/test_gpu_gru_bwd.py case o) at tests/gru_bwd_cases.py's bound."""
     env = dict(os.environ, TOUED_GRU_F32="1")
     r = subprocess.run([sys.executable, str(ROOT / "tests" / "gru_f32_worker.py")], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=300)
@@ -383,3 +384,9 @@ def test_f32_fallback_process():
     assert len(res["bwd"]) == 16, sorted(res["bwd"])
     bad = {k: v for k, v in res["bwd"].items() if not v < 1e-4}
     assert not bad, res["bwd"]
+    assert res["bwd_matrix_instance"] == {"a": "k_gru_bwd<1>", "c-T1": "k_gru_bwd<1>"}
+    for tag, tab in res["bwd_matrix"].items():
+        assert {"dr_pre/kt", "dz_pre/r", "dhn", "dn_pre/r", "dh_heads", "relu_out", "dX3/r", "dX4/kt", "GI_in/row",
+                "GI_heads/row", "hr_w/row", "in_w/row", "pi_b", "y_b"} <= set(tab), (tag, sorted(tab))
+        import gru_bwd_cases as bc
+        bc.assert_within(f"TOUED_GRU_F32=1 bwd {tag}", {k: tuple(v) for k, v in tab.items()})
