@@ -250,6 +250,32 @@ int toued_plr_sample_prio(int B, int N, const float* score, const uint8_t* activ
                           float staleness_coeff, float p_replay, int* chosen, int* rep, int* rnd, int* use_out,
                           float* p_out, hipStream_t stream);
 
+/* ---- Double-oracle Nash solver (environments/nash_sampler.py, util/projection.py) ---- */
+/* projection_simplex (util/projection.py:9-37) over R rows of length B: out[r][:nz[r]] is the Euclidean projection of
+ * x[r][:nz[r]] onto the unit simplex, out[r][nz[r]:] is exactly 0 and x[r][nz[r]:] is not read.  x, out [R][B];
+ * nz [R] is a device array: it is not checked on the host, the kernel clamps each entry into [1, B].  One workgroup
+ * per row and no sort: Newton's iteration on tau (sum_j max(x_j - tau, 0) = 1) with f64 sums in a fixed order, so the
+ * result has no tie order, is run-to-run bit-identical and is max(x - tau, 0) rounded to f32 once.  out may alias x.
+ * -1 for negative R, B outside [1, 8192], or (with R > 0) a null pointer; R == 0 succeeds. */
+int toued_project_simplex(const float* x, const int* nz, int R, int B, float* out, hipStream_t stream);
+/* 1 if toued_nash_solve takes this B (1 <= B <= 128: the payoff matrix is held in registers), else 0 */
+int toued_nash_fits(int B);
+/* get_nash (nash_sampler.py:39-58) for G independent zero-sum games in one launch, one workgroup per game:
+ * payoff [G][B][B] row-major (x, the row player, minimises x^T M y), nx, ny [G], x0, y0 [G][B].  From the start
+ * strategies, used as given (nothing is re-projected), every iteration takes both steps from the old pair,
+ *   x' = P_nx(x - lr (M y)),  y' = P_ny(y + lr (x^T M)),  P_n = toued_project_simplex's projection of the first n,
+ * and x_avg, y_avg [G][B] are the means of the iters + 1 iterates, the start included (iters == 0 returns x0, y0 bit
+ * for bit).  The iteration runs in f64 throughout (an f32 iterate drifts from the float64 iteration by up to half an
+ * ulp per step while the gradient is constant); lr enters as the f32 it is passed as.  stats [G][2] = {x_avg^T M y_avg, max_{j < ny}
+ * (x_avg^T M)_j - min_{i < nx} (M y_avg)_i}: the game value and the exploitability of the returned (f32) averages,
+ * computed in f64 and rounded once.  Rows >= nx and columns >= ny of the payoff are read as zeros, whatever they
+ * hold.  nx, ny are device arrays: they are not checked on the host, the kernel clamps them into [1, B].  The whole
+ * loop runs on chip (matrix in registers, strategies exchanged through LDS, workgroup barriers only, no atomics):
+ * run-to-run bit-identical, and game g's result depends on game g's inputs only.  -1 for B where toued_nash_fits is
+ * 0, negative G, iters outside [0, 1000000], a non-finite lr, or (with G > 0) a null pointer; G == 0 succeeds. */
+int toued_nash_solve(const float* payoff, const int* nx, const int* ny, const float* x0, const float* y0, int G, int B,
+                     int iters, float lr, float* x_avg, float* y_avg, float* stats, hipStream_t stream);
+
 /* ---- Agents (agents/agents.py:31-95; models/agent.py:7-45) ---- */
 /* Dense(cols, use_bias=False) lecun_normal kernels [n][D][cols]: truncated_normal(keys[i]) in
  * [lo, hi] = erf(-+2/sqrt2), times stddev.  keys are the flax per-param keys (toued/agents.py). */

@@ -13,8 +13,14 @@ def __getattr__(name):
     if name in ("create_lpg_train_state", "make_lpg_train_step", "LpgTrainState", "ValueCriticStates"):
         from . import meta
         return getattr(meta, name)
+    # the double-oracle sampler's game solver (environments/nash_sampler.py, util/projection.py)
+    if name in ("project_simplex", "solve_nash", "initial_strategies", "training_level_ids", "cross_regret",
+                "NashSolution"):
+        from . import nash
+        return getattr(nash, name)
     raise AttributeError(name)
 
 
 __all__ = ["ToUEDError", "lib", "create_lpg_train_state", "make_lpg_train_step", "LpgTrainState",
-           "ValueCriticStates"]
+           "ValueCriticStates", "project_simplex", "solve_nash", "initial_strategies", "training_level_ids",
+           "cross_regret", "NashSolution"]

@@ -119,6 +119,9 @@ _SIGS = {
     "toued_optimal_return": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
     "toued_policy_return": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "toued_policy_return_moments": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "toued_project_simplex": [_P, _P, _I, _I, _P, _P],
+    "toued_nash_fits": [_I],
+    "toued_nash_solve": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "toued_dbg_wgrad_last_ntiles": [],
     "toued_a2c_chain": [EnvSpecC, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _P, _P],
     "toued_a2c_chain_self": [EnvSpecC, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P, _P, _P],
