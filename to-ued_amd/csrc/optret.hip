@@ -25,9 +25,20 @@
 //   * Only the count of unmasked steps matters (v_t is zero for t >= max_steps_in_episode): H = min(max_steps,
 //     max_rollout_len) backups give v_0, and the rows t >= max_steps of v_all are zero fills.
 //
-// k_policy_return (further down) is the same recursion for the expected return of a tabular agent's own policy,
-// v_t(s) = sum_a pi_t(a|s) q(s, a), on the same setup (optret_setup).  k_policy_moments (after it) adds the variance
-// of that return, u_t(s) = Var[G_t | s], in two f32 tables behind the setup's LDS.
+// k_policy_return is the same recursion for the expected return of a tabular agent's own policy,
+// v_t(s) = sum_a pi_t(a|s) q(s, a), and k_policy_moments adds the variance of that return, u_t(s) = Var[G_t | s], in
+// two f32 tables behind the setup's LDS.  The three kernels are built from the same parts; a further recursion on
+// these tables is a backup function on top of outcome_loop and a kernel with its time loop:
+//   optret_setup     the per-level tables                                     all three
+//   work_item        work item -> (cell, existence mask)                      all three
+//   outcome_loop     an item's next states and E[v'] (and E[u' + v'^2])       all three
+//   step_end         a step's barrier, v_all (var_all) row stores, table swap  all three
+//   write_start      v0 (var0) at the start state                             all three
+//   softmax_backup   sum_a pi(a) q(s, a) (and the variance beside it)         k_policy_return, k_policy_moments
+//   policy_items     a thread's items and their theta rows in registers       k_policy_return, k_policy_moments
+// k_optimal_return's backup, the max over the actions, is written in the kernel.
+#include <type_traits>
+
 #include "env_dev.h"
 
 namespace {
@@ -157,247 +168,43 @@ __device__ __forceinline__ OptretSetup optret_setup(unsigned char* smem, const i
   return OptretSetup{va, pw, rsum, keepw, lev, nxt, cells, eord, G2, S, NE, used, ne, H, s_ncell};
 }
 
-__global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, int n_max, int L,
-                                 float* __restrict__ v0, float* __restrict__ v_all) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
-  double* const va = T.va;
-  const double *pw = T.pw, *rsum = T.rsum, *keepw = T.keepw;
-  const int* lev = T.lev;
-  const uint16_t* nxt = T.nxt;
-  const uint8_t *cells = T.cells, *eord = T.eord;
-  const int G2 = T.G2, S = T.S, NE = T.NE, used = T.used, ne = T.ne, H = T.H;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const float ninf = -__builtin_inff();
-
-  const int ncell = T.ncell;
-  const int nwork = ncell * ne;
-  int curo = 0;    // v_t, written: table va (offset 0) or vb (offset S) of the 2S-entry array
-  int nxo = S;     // v_{t+1}, read
-  for (int t = H - 1; t >= 0; --t) {
-    for (int w = tid; w < nwork; w += nt) {
-      const int ei = w / ncell;
-      const int e = eord[ei], pos = cells[w - ei * ncell];
-      const int absent = used & ~e;
-      const double* pwa = pw + absent * NE;
-      int base[5];
-      double r[5], keep[5], ev[5];
-#pragma unroll
-      for (int a = 0; a < 5; ++a) {
-        const uint32_t en = nxt[pos * 5 + a];
-        const int c = (int)(en >> 8) & e;
-        base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~c);
-        r[a] = rsum[c];
-        keep[a] = keepw[c];
-        ev[a] = 0.0;
-      }
-      // the subsets R of `absent`, two per round: one weight read serves the five actions, and the ten value reads
-      // of a round are independent.  Every value read is a valid state's (finite), so a zero weight gives a zero
-      // term without a test; a second subset that does not exist reads subset 0 with weight 0.
-      int R0 = 0;
-      do {
-        const int R1 = (R0 - absent) & absent;
-        const double p0 = pwa[R0];
-        const double p1 = pw[R1 != 0 ? absent * NE + R1 : NE * NE];   // pw[NE * NE] = 0
-        const int o0 = G2 * R0, o1 = G2 * R1;
-        double x0[5], x1[5];
-#pragma unroll
-        for (int a = 0; a < 5; ++a) { x0[a] = va[base[a] + o0]; x1[a] = va[base[a] + o1]; }
-        __builtin_amdgcn_sched_barrier(0);   // all twelve reads in flight before the first fma waits
-#pragma unroll
-        for (int a = 0; a < 5; ++a) ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
-        R0 = R1 != 0 ? (R1 - absent) & absent : 0;
-      } while (R0 != 0);
-      double best = (double)ninf;
-#pragma unroll
-      for (int a = 0; a < 5; ++a) {
-        const double q = r[a] + ev[a] * keep[a];
-        best = q > best ? q : best;
-      }
-      va[curo + pos + G2 * e] = best;
-    }
-    lds_barrier();
-    if (v_all != nullptr) {
-      float* row = v_all + ((size_t)blockIdx.x * L + t) * S;
-      for (int s = tid; s < S; s += nt) row[s] = (float)va[curo + s];
-    }
-    const int sw = curo; curo = nxo; nxo = sw;
-  }
-  // table nxo now holds v_0 (v0 is 0 when H == 0, whatever the start cell)
-  if (tid == 0) v0[blockIdx.x] = H > 0 ? (float)va[nxo + lev[L_START] + G2 * used] : 0.0f;
+// Work item w (< ncell * ne) in the setup's order: its existence mask and cell.
+__device__ __forceinline__ void work_item(const OptretSetup& T, int w, int& pos, int& e) {
+  const int ei = w / T.ncell;
+  e = T.eord[ei];
+  pos = T.cells[w - ei * T.ncell];
 }
 
-// One policy backup: v_t(pos, e) = sum_a pi(a) q(s, a) into table `curo`, with the policy's f32 logits l[5] (as
-// actor_probs5 forms them) and k_optimal_return's outcome loop on table `nxo`.  The softmax is exp(l - max) / sum in
-// f64; the argmax term is exp(0) = 1, so the sum is >= 1: huge logits give an exact one-hot policy and no NaN.
-__device__ __forceinline__ void policy_backup(const OptretSetup& T, int nxo, int curo, int pos, int e,
-                                              const float* l) {
-  double* const va = T.va;
-  const double* pw = T.pw;
-  const int G2 = T.G2, NE = T.NE;
-  const int absent = T.used & ~e;
-  const double* pwa = pw + absent * NE;
-  int base[5], col[5];
-  double ev[5];
-#pragma unroll
-  for (int a = 0; a < 5; ++a) {
-    const uint32_t en = T.nxt[pos * 5 + a];
-    col[a] = (int)(en >> 8) & e;
-    base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~col[a]);
-    ev[a] = 0.0;
-  }
-  int R0 = 0;
-  do {
-    const int R1 = (R0 - absent) & absent;
-    const double p0 = pwa[R0];
-    const double p1 = pw[R1 != 0 ? absent * NE + R1 : NE * NE];   // pw[NE * NE] = 0
-    const int o0 = G2 * R0, o1 = G2 * R1;
-    double x0[5], x1[5];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) { x0[a] = va[base[a] + o0]; x1[a] = va[base[a] + o1]; }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int a = 0; a < 5; ++a) ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
-    R0 = R1 != 0 ? (R1 - absent) & absent : 0;
-  } while (R0 != 0);
-  float m = l[0];
-#pragma unroll
-  for (int a = 1; a < 5; ++a) m = fmaxf(m, l[a]);
-  double num = 0.0, den = 0.0;
-#pragma unroll
-  for (int a = 0; a < 5; ++a) {
-    const double x = exp((double)l[a] - (double)m);
-    const double q = T.rsum[col[a]] + ev[a] * T.keepw[col[a]];
-    den += x;
-    num = __builtin_fma(x, q, num);
-  }
-  va[curo + pos + G2 * e] = num / den;
-}
-
-// Exact expected return of a tabular agent's own policy: k_optimal_return's recursion with
-//   v_t(s) = sum_a pi_t(a|s) q(s, a),   pi_t(.|s) = softmax(theta[s] + fl(fl(t * 0.001) * theta[D-1]))
-// in place of the max.  The logits are formed in f32 by actor_probs5's two rounded operations; the softmax and the
-// backup are f64.  One workgroup per (level, table) pair with the setup, work order and outcome loop above.  Work item
-// w belongs to thread w % blockDim at every step, so a thread reads the theta rows of its first ITEMS items once,
-// before the time loop, and keeps them in registers (the item loop is unrolled over ITEMS, so the rows are not
-// runtime-indexed).  Every mode's table has at most 6 items per thread and runs with MORE = false: theta is not read
-// inside the time loop.  MORE = true serves larger tables, which no mode has: the items past the first ITEMS go
-// through a plain loop that reads their rows from global memory at every step.
-template <int ITEMS, bool MORE>
-__global__ __launch_bounds__(1024) void k_policy_return(const int* __restrict__ levels,
-                                                        const float* __restrict__ theta, int D, int max_grid,
-                                                        int n_max, int L, float* __restrict__ v0,
-                                                        float* __restrict__ v_all) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+// The outcomes of the five actions in state (pos, e), read from table `nxo`: col[a], the objects the move collects,
+// ev[a] = E[v'] over the subsets R of the absent objects that respawn and, with VAR, ez[a] = E[u' + v'^2] with the
+// next state's variance u' read as f32 from ua (one more LDS read and one more accumulation per outcome).
+// after_cols() runs once col[] is known and before the loop: k_optimal_return's reads by col[] start there.  (As two
+// helpers, next states and loop, with those reads between them, k_optimal_return measured 1 % slower on 4000 `all`
+// levels.)
+// The loop takes two subsets per round: one weight read serves the five actions, and the ten value reads of a round
+// are independent.  Every value read is a valid state's (finite), so a zero weight gives a zero term without a test; a
+// second subset that does not exist reads subset 0 with weight 0.
+template <bool VAR, class AfterCols>
+__device__ __forceinline__ void outcome_loop(const OptretSetup& T, const float* ua, int nxo, int pos, int e, int* col,
+                                             double* ev, double* ez, AfterCols after_cols) {
   const double* va = T.va;
-  const int G2 = T.G2, S = T.S, H = T.H;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = T.ncell;
-  const int nwork = ncell * T.ne;      // <= S; <= ITEMS * blockDim without MORE (the host's choice of ITEMS)
-
-  const float* th = theta + (size_t)blockIdx.x * D * 5;
-  float last[5];
-#pragma unroll
-  for (int a = 0; a < 5; ++a) last[a] = th[(size_t)(D - 1) * 5 + a];
-  int st[ITEMS];          // pos | e << 8 of the thread's item k, -1 past the level's work
-  float row[ITEMS][5];
-#pragma unroll
-  for (int k = 0; k < ITEMS; ++k) {
-    const int w = tid + k * nt;
-    st[k] = -1;
-#pragma unroll
-    for (int a = 0; a < 5; ++a) row[k][a] = 0.0f;
-    if (w < nwork) {
-      const int ei = w / ncell;
-      const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
-      st[k] = pos | (e << 8);
-      const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
-#pragma unroll
-      for (int a = 0; a < 5; ++a) row[k][a] = r[a];
-    }
-  }
-
-  int curo = 0;    // v_t, written
-  int nxo = S;     // v_{t+1}, read
-  for (int t = H - 1; t >= 0; --t) {
-    const float c = __fmul_rn((float)t, 0.001f);
-    float tl[5];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) tl[a] = __fmul_rn(c, last[a]);
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-      if (st[k] < 0) continue;
-      float l[5];
-#pragma unroll
-      for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
-      policy_backup(T, nxo, curo, st[k] & 0xFF, st[k] >> 8, l);
-    }
-    if (MORE) {
-      for (int w = tid + ITEMS * nt; w < nwork; w += nt) {
-        const int ei = w / ncell;
-        const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
-        const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
-        float l[5];
-#pragma unroll
-        for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(r[a], tl[a]);
-        policy_backup(T, nxo, curo, pos, e, l);
-      }
-    }
-    lds_barrier();
-    if (v_all != nullptr) {
-      float* out = v_all + ((size_t)blockIdx.x * L + t) * S;
-      for (int s = tid; s < S; s += nt) out[s] = (float)va[curo + s];
-    }
-    const int sw = curo; curo = nxo; nxo = sw;
-  }
-  if (tid == 0) v0[blockIdx.x] = H > 0 ? (float)va[nxo + T.lev[L_START] + G2 * T.used] : 0.0f;
-}
-
-template <int ITEMS, bool MORE>
-int launch_policy_return(int n, int block, size_t lds, hipStream_t stream, const int* levels, const float* theta, int D,
-                         int max_grid, int n_max, int L, float* v0, float* v_all) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_return<ITEMS, MORE>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
-                  "toued_policy_return: cannot raise the dynamic LDS limit");
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_policy_return<ITEMS, MORE>), dim3(n), dim3(block), lds, stream, levels, theta, D, max_grid,
-                     n_max, L, v0, v_all);
-  TOUED_CHECK_LAUNCH();
-  return 0;
-}
-
-// dynamic LDS of k_policy_moments: optret_setup's layout (a multiple of 16 bytes), then f32 ua[S], ub[S]
-__host__ __device__ inline size_t polmom_lds_bytes(int G2, int n_max) {
-  return optret_lds_bytes(G2, n_max) + 2 * ((size_t)G2 << n_max) * sizeof(float);
-}
-
-// policy_backup with the return's variance beside its mean: v_t(pos, e) into table `curo` of va by policy_backup's
-// arithmetic, operation for operation, and u_t(pos, e) = Var[G_t | s] into table `curo` of ua.  With v', u' the
-// next state's mean and variance, the second moment of r + cont * G' given (s, a) is
-//   m2(s, a) = r^2 + c * (2 r E[v'] + E[u' + v'^2]),   c = 1 - p_term,
-// and u_t(s) = sum_a pi(a) m2(s, a) - v_t(s)^2 (the law of total variance, nothing clipped: c < 0 is taken as the
-// mean takes it).  u' is read as f32 and everything else is f64; per outcome one more LDS read, u' + v'^2 and one
-// more accumulation than the mean's.
-__device__ __forceinline__ void moments_backup(const OptretSetup& T, float* ua, int nxo, int curo, int pos, int e,
-                                               const float* l) {
-  double* const va = T.va;
   const double* pw = T.pw;
   const int G2 = T.G2, NE = T.NE;
   const int absent = T.used & ~e;
   const double* pwa = pw + absent * NE;
-  int base[5], col[5];
-  double ev[5], ez[5];
+  int base[5];            // index in table nxo of (next cell, e without col[a]); an outcome adds G2 * R
+  double sv[5], sz[5];    // the sums, in registers whatever ev and ez point to
 #pragma unroll
   for (int a = 0; a < 5; ++a) {
     const uint32_t en = T.nxt[pos * 5 + a];
     col[a] = (int)(en >> 8) & e;
     base[a] = nxo + (int)(en & 0xFFu) + G2 * (e & ~col[a]);
-    ev[a] = 0.0;
-    ez[a] = 0.0;
+  }
+  after_cols();
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    sv[a] = 0.0;
+    if constexpr (VAR) sz[a] = 0.0;
   }
   int R0 = 0;
   do {
@@ -411,19 +218,109 @@ __device__ __forceinline__ void moments_backup(const OptretSetup& T, float* ua, 
     for (int a = 0; a < 5; ++a) {
       x0[a] = va[base[a] + o0];
       x1[a] = va[base[a] + o1];
-      y0[a] = ua[base[a] + o0];
-      y1[a] = ua[base[a] + o1];
+      if constexpr (VAR) {
+        y0[a] = ua[base[a] + o0];
+        y1[a] = ua[base[a] + o1];
+      }
     }
-    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);   // all the round's reads in flight before the first fma waits
 #pragma unroll
     for (int a = 0; a < 5; ++a) {
-      ev[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], ev[a]));
-      const double z0 = __builtin_fma(x0[a], x0[a], (double)y0[a]);
-      const double z1 = __builtin_fma(x1[a], x1[a], (double)y1[a]);
-      ez[a] = __builtin_fma(p1, z1, __builtin_fma(p0, z0, ez[a]));
+      sv[a] = __builtin_fma(p1, x1[a], __builtin_fma(p0, x0[a], sv[a]));
+      if constexpr (VAR) {
+        const double z0 = __builtin_fma(x0[a], x0[a], (double)y0[a]);
+        const double z1 = __builtin_fma(x1[a], x1[a], (double)y1[a]);
+        sz[a] = __builtin_fma(p1, z1, __builtin_fma(p0, z0, sz[a]));
+      }
     }
     R0 = R1 != 0 ? (R1 - absent) & absent : 0;
   } while (R0 != 0);
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    ev[a] = sv[a];
+    if constexpr (VAR) ez[a] = sz[a];
+  }
+}
+
+// Ends step t: one LDS-only barrier, the optional row t of v_all (var_all), and the tables swap.
+template <bool VAR>
+__device__ __forceinline__ void step_end(const OptretSetup& T, const float* ua, int L, int t, float* v_all,
+                                         float* var_all, int& curo, int& nxo) {
+  const double* va = T.va;
+  const int S = T.S;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  lds_barrier();
+  if (v_all != nullptr) {
+    float* out = v_all + ((size_t)blockIdx.x * L + t) * S;
+    for (int s = tid; s < S; s += nt) out[s] = (float)va[curo + s];
+  }
+  if constexpr (VAR) {
+    if (var_all != nullptr) {
+      float* out = var_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) out[s] = ua[curo + s];
+    }
+  }
+  const int sw = curo; curo = nxo; nxo = sw;
+}
+
+// After the last step table nxo holds v_0 (u_0): thread 0 writes them at the start state, 0 when H == 0
+template <bool VAR>
+__device__ __forceinline__ void write_start(const OptretSetup& T, const float* ua, int nxo, float* v0, float* var0) {
+  if (threadIdx.x == 0) {
+    const int si = nxo + T.lev[L_START] + T.G2 * T.used;
+    v0[blockIdx.x] = T.H > 0 ? (float)T.va[si] : 0.0f;
+    if constexpr (VAR) var0[blockIdx.x] = T.H > 0 ? ua[si] : 0.0f;
+  }
+}
+
+__global__ void k_optimal_return(const int* __restrict__ levels, int max_grid, int n_max, int L,
+                                 float* __restrict__ v0, float* __restrict__ v_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int nwork = T.ncell * T.ne;
+  int curo = 0;    // v_t, written: table va (offset 0) or vb (offset S) of the 2S-entry array
+  int nxo = T.S;   // v_{t+1}, read
+  for (int t = T.H - 1; t >= 0; --t) {
+    for (int w = tid; w < nwork; w += nt) {
+      int pos, e;
+      work_item(T, w, pos, e);
+      int col[5];
+      double r[5], keep[5], ev[5];
+      outcome_loop<false>(T, nullptr, nxo, pos, e, col, ev, nullptr, [&] {
+#pragma unroll
+        for (int a = 0; a < 5; ++a) {
+          r[a] = T.rsum[col[a]];
+          keep[a] = T.keepw[col[a]];
+        }
+      });
+      double best = (double)-__builtin_inff();
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        const double q = r[a] + ev[a] * keep[a];
+        best = q > best ? q : best;
+      }
+      T.va[curo + pos + T.G2 * e] = best;
+    }
+    step_end<false>(T, nullptr, L, t, v_all, nullptr, curo, nxo);
+  }
+  write_start<false>(T, nullptr, nxo, v0, nullptr);
+}
+
+// One policy backup: v_t(pos, e) = sum_a pi(a) q(s, a) into table `curo` of va, with the policy's f32 logits l[5] (as
+// actor_probs5 forms them) and the outcome loop on table `nxo`.  The softmax is exp(l - max) / sum in f64; the argmax
+// term is exp(0) = 1, so the sum is >= 1: huge logits give an exact one-hot policy and no NaN.
+// With VAR, the return's variance beside its mean, by the same statements: u_t(pos, e) = Var[G_t | s] into table
+// `curo` of ua.  With v', u' the next state's mean and variance, the second moment of r + cont * G' given (s, a) is
+//   m2(s, a) = r^2 + c * (2 r E[v'] + E[u' + v'^2]),   c = 1 - p_term,
+// and u_t(s) = sum_a pi(a) m2(s, a) - v_t(s)^2 (the law of total variance, nothing clipped: c < 0 is taken as the
+// mean takes it).  Everything but u' is f64; u_t is rounded to f32 once.
+template <bool VAR>
+__device__ __forceinline__ void softmax_backup(const OptretSetup& T, float* ua, int nxo, int curo, int pos, int e,
+                                               const float* l) {
+  int col[5];
+  double ev[5], ez[5];
+  outcome_loop<VAR>(T, ua, nxo, pos, e, col, ev, ez, [] {});
   float m = l[0];
 #pragma unroll
   for (int a = 1; a < 5; ++a) m = fmaxf(m, l[a]);
@@ -435,17 +332,103 @@ __device__ __forceinline__ void moments_backup(const OptretSetup& T, float* ua, 
     const double q = r + ev[a] * keep;
     den += x;
     num = __builtin_fma(x, q, num);
-    const double m2 = __builtin_fma(keep, __builtin_fma(r + r, ev[a], ez[a]), r * r);
-    num2 = __builtin_fma(x, m2, num2);
+    if constexpr (VAR) {
+      const double m2 = __builtin_fma(keep, __builtin_fma(r + r, ev[a], ez[a]), r * r);
+      num2 = __builtin_fma(x, m2, num2);
+    }
   }
   const double v = num / den;
-  va[curo + pos + G2 * e] = v;
-  ua[curo + pos + G2 * e] = (float)(num2 / den - v * v);
+  T.va[curo + pos + T.G2 * e] = v;
+  if constexpr (VAR) ua[curo + pos + T.G2 * e] = (float)(num2 / den - v * v);
+}
+
+// Work item w belongs to thread w % blockDim at every step, so a thread reads the theta rows of its first ITEMS items
+// once, before the time loop, and keeps them in registers (the kernels unroll their item loop over ITEMS, so the rows
+// are not runtime-indexed): st[k] = pos | e << 8 of the thread's item k, -1 past the level's work, row[k] its logits
+// row, and last = theta[D-1], the time feature's row.
+template <int ITEMS>
+__device__ __forceinline__ void policy_items(const OptretSetup& T, const float* th, int D, int nwork,
+                                             float (&last)[5], int (&st)[ITEMS], float (&row)[ITEMS][5]) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) last[a] = th[(size_t)(D - 1) * 5 + a];
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) {
+    const int w = tid + k * nt;
+    st[k] = -1;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) row[k][a] = 0.0f;
+    if (w < nwork) {
+      int pos, e;
+      work_item(T, w, pos, e);
+      st[k] = pos | (e << 8);
+      const float* r = th + (size_t)(pos + T.G2 * e) * 5;      // pos + G2 * e < S = D - 1
+#pragma unroll
+      for (int a = 0; a < 5; ++a) row[k][a] = r[a];
+    }
+  }
+}
+
+// Exact expected return of a tabular agent's own policy: k_optimal_return's recursion with
+//   v_t(s) = sum_a pi_t(a|s) q(s, a),   pi_t(.|s) = softmax(theta[s] + fl(fl(t * 0.001) * theta[D-1]))
+// in place of the max.  The logits are formed in f32 by actor_probs5's rounded operations; the softmax and the
+// backup are f64.  One workgroup per (level, table) pair; theta rows in registers by policy_items.  Every mode's table
+// has at most 6 items per thread and runs with MORE = false: theta is not read inside the time loop.  MORE = true
+// serves larger tables, which no mode has: the items past the first ITEMS go through a plain loop that reads their
+// rows from global memory at every step.
+template <int ITEMS, bool MORE>
+__global__ __launch_bounds__(1024) void k_policy_return(const int* __restrict__ levels,
+                                                        const float* __restrict__ theta, int D, int max_grid,
+                                                        int n_max, int L, float* __restrict__ v0,
+                                                        float* __restrict__ v_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int nwork = T.ncell * T.ne;      // <= S; <= ITEMS * blockDim without MORE (the host's choice of ITEMS)
+  const float* th = theta + (size_t)blockIdx.x * D * 5;
+  float last[5], row[ITEMS][5];
+  int st[ITEMS];
+  policy_items(T, th, D, nwork, last, st, row);
+
+  int curo = 0;    // v_t, written
+  int nxo = T.S;   // v_{t+1}, read
+  for (int t = T.H - 1; t >= 0; --t) {
+    const float c = __fmul_rn((float)t, 0.001f);
+    float tl[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) tl[a] = __fmul_rn(c, last[a]);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      if (st[k] < 0) continue;
+      float l[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
+      softmax_backup<false>(T, nullptr, nxo, curo, st[k] & 0xFF, st[k] >> 8, l);
+    }
+    if (MORE) {
+      for (int w = tid + ITEMS * nt; w < nwork; w += nt) {
+        int pos, e;
+        work_item(T, w, pos, e);
+        const float* r = th + (size_t)(pos + T.G2 * e) * 5;      // pos + G2 * e < S = D - 1
+        float l[5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(r[a], tl[a]);
+        softmax_backup<false>(T, nullptr, nxo, curo, pos, e, l);
+      }
+    }
+    step_end<false>(T, nullptr, L, t, v_all, nullptr, curo, nxo);
+  }
+  write_start<false>(T, nullptr, nxo, v0, nullptr);
+}
+
+// dynamic LDS of k_policy_moments: optret_setup's layout (a multiple of 16 bytes), then f32 ua[S], ub[S]
+__host__ __device__ inline size_t polmom_lds_bytes(int G2, int n_max) {
+  return optret_lds_bytes(G2, n_max) + 2 * ((size_t)G2 << n_max) * sizeof(float);
 }
 
 // Mean and variance of the first-episode return of a tabular agent's own policy: k_policy_return (its setup, work
-// order, block size and mean arithmetic: v0 and v_all are bit-identical to its) with a second table pair for
-// u_t(s) = Var[G_t | s], see moments_backup.  The u tables are f32, double-buffered in LDS behind optret_setup's
+// order, block size and, through softmax_backup, its mean arithmetic: v0 and v_all are bit-identical to its) with a
+// second table pair for u_t(s) = Var[G_t | s].  The u tables are f32, double-buffered in LDS behind optret_setup's
 // layout (two more f64 tables would not fit the largest mode), indexed like va; every step's arithmetic is f64 and
 // the f32 store of u_t is the step's only rounding that the f64 recursion does not have.  Invalid states hold -inf in
 // both u tables, as in va, and are never read by a valid state's backup.  A table that fits the LDS with the u tables
@@ -458,47 +441,26 @@ __global__ __launch_bounds__(1024) void k_policy_moments(const int* __restrict__
                                                          float* __restrict__ var_all) {
   extern __shared__ __align__(16) unsigned char smem[];
   const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, v_all);
-  const double* va = T.va;
-  const int G2 = T.G2, S = T.S, H = T.H;
-  float* const ua = reinterpret_cast<float*>(smem + optret_lds_bytes(G2, n_max));
+  const int S = T.S;
+  float* const ua = reinterpret_cast<float*>(smem + optret_lds_bytes(T.G2, n_max));
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int ncell = T.ncell;
-  const int nwork = ncell * T.ne;      // <= S <= ITEMS * blockDim (the host's choice of ITEMS)
+  const int nwork = T.ncell * T.ne;      // <= S <= ITEMS * blockDim (the host's choice of ITEMS)
 
   // both u tables: u_H = 0 at the valid states, -inf at the invalid ones (va's fill); zero rows of var_all
-  for (int s = tid; s < S; s += nt) ua[s] = ua[S + s] = (float)va[s];
+  for (int s = tid; s < S; s += nt) ua[s] = ua[S + s] = (float)T.va[s];
   if (var_all != nullptr) {
-    float* rows = var_all + ((size_t)blockIdx.x * L + H) * S;
-    const size_t nz = (size_t)(L - H) * S;
+    float* rows = var_all + ((size_t)blockIdx.x * L + T.H) * S;
+    const size_t nz = (size_t)(L - T.H) * S;
     for (size_t i = tid; i < nz; i += nt) rows[i] = 0.0f;
   }
-
-  const float* th = theta + (size_t)blockIdx.x * D * 5;
-  float last[5];
-#pragma unroll
-  for (int a = 0; a < 5; ++a) last[a] = th[(size_t)(D - 1) * 5 + a];
-  int st[ITEMS];          // pos | e << 8 of the thread's item k, -1 past the level's work
-  float row[ITEMS][5];
-#pragma unroll
-  for (int k = 0; k < ITEMS; ++k) {
-    const int w = tid + k * nt;
-    st[k] = -1;
-#pragma unroll
-    for (int a = 0; a < 5; ++a) row[k][a] = 0.0f;
-    if (w < nwork) {
-      const int ei = w / ncell;
-      const int e = T.eord[ei], pos = T.cells[w - ei * ncell];
-      st[k] = pos | (e << 8);
-      const float* r = th + (size_t)(pos + G2 * e) * 5;      // pos + G2 * e < S = D - 1
-#pragma unroll
-      for (int a = 0; a < 5; ++a) row[k][a] = r[a];
-    }
-  }
+  float last[5], row[ITEMS][5];
+  int st[ITEMS];
+  policy_items(T, theta + (size_t)blockIdx.x * D * 5, D, nwork, last, st, row);
   __syncthreads();
 
   int curo = 0;    // v_t and u_t, written
   int nxo = S;     // v_{t+1} and u_{t+1}, read
-  for (int t = H - 1; t >= 0; --t) {
+  for (int t = T.H - 1; t >= 0; --t) {
     const float c = __fmul_rn((float)t, 0.001f);
     float tl[5];
 #pragma unroll
@@ -510,44 +472,64 @@ __global__ __launch_bounds__(1024) void k_policy_moments(const int* __restrict__
       // hoisted out of the time loop for all ITEMS items at once (ITEMS = 4 and 6 spilled to scratch that way)
       int sk = st[k];
       asm volatile("" : "+v"(sk));
-      const int pos = sk & 0xFF, e = sk >> 8;
       float l[5];
 #pragma unroll
       for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
-      moments_backup(T, ua, nxo, curo, pos, e, l);
+      softmax_backup<true>(T, ua, nxo, curo, sk & 0xFF, sk >> 8, l);
     }
-    lds_barrier();
-    if (v_all != nullptr) {
-      float* out = v_all + ((size_t)blockIdx.x * L + t) * S;
-      for (int s = tid; s < S; s += nt) out[s] = (float)va[curo + s];
-    }
-    if (var_all != nullptr) {
-      float* out = var_all + ((size_t)blockIdx.x * L + t) * S;
-      for (int s = tid; s < S; s += nt) out[s] = ua[curo + s];
-    }
-    const int sw = curo; curo = nxo; nxo = sw;
+    step_end<true>(T, ua, L, t, v_all, var_all, curo, nxo);
   }
-  if (tid == 0) {
-    const int si = nxo + T.lev[L_START] + G2 * T.used;
-    v0[blockIdx.x] = H > 0 ? (float)va[si] : 0.0f;
-    var0[blockIdx.x] = H > 0 ? ua[si] : 0.0f;
-  }
+  write_start<true>(T, ua, nxo, v0, var0);
 }
 
-template <int ITEMS>
-int launch_policy_moments(int n, int block, size_t lds, hipStream_t stream, const int* levels, const float* theta,
-                          int D, int max_grid, int n_max, int L, float* v0, float* var0, float* v_all,
-                          float* var_all) {
+// Raises kernel K's dynamic-LDS limit on its first launch, then launches it: one workgroup of `block` threads per
+// level.  `who` is the entry point, for the messages.
+template <auto K, class... Args>
+int optret_launch(const char* who, int n, int block, size_t lds, hipStream_t stream, Args... args) {
   static bool attr_set = false;
   if (!attr_set) {
-    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_moments<ITEMS>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
-                  "toued_policy_return_moments: cannot raise the dynamic LDS limit");
+    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kOptretLdsMax) == hipSuccess,
+                  "%s: cannot raise the dynamic LDS limit", who);
     attr_set = true;
   }
-  hipLaunchKernelGGL((k_policy_moments<ITEMS>), dim3(n), dim3(block), lds, stream, levels, theta, D, max_grid, n_max,
-                     L, v0, var0, v_all, var_all);
-  TOUED_CHECK_LAUNCH();
+  hipLaunchKernelGGL(K, dim3(n), dim3(block), lds, stream, args...);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {      // TOUED_CHECK_LAUNCH under the entry point's name: -2, a launch failure
+    toued::set_error("%s: launch failed: %s", who, hipGetErrorString(err));
+    return -2;
+  }
+  return 0;
+}
+
+// launch(integral_constant<int, I>) for the fewest work items per thread I of 1, 2, 4, 6 that hold `items`
+template <class Launch>
+int by_items(int items, Launch launch) {
+  if (items <= 1) return launch(std::integral_constant<int, 1>{});
+  if (items <= 2) return launch(std::integral_constant<int, 2>{});
+  if (items <= 4) return launch(std::integral_constant<int, 4>{});
+  return launch(std::integral_constant<int, 6>{});      // every mode's table
+}
+
+// block size from the table size: one state per thread up to 1024 threads
+int optret_block(int S) { return S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024)); }
+
+// The entry points' argument checks.  `who` is the entry point; D is null where there is no theta; lds_bytes is the
+// kernel's dynamic LDS, returned in *lds.
+int optret_check(const char* who, int tabular, int n, int max_rollout_len, int max_grid, int n_max, const int* D,
+                 size_t (*lds_bytes)(int, int), size_t* lds) {
+  TOUED_REQUIRE(tabular != 0, "%s: non-tabular environments are unsupported (%s)", who,
+                D == nullptr ? "the reference raises NotImplementedError"
+                             : "the agent is not a table over the environment's states");
+  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "%s: n=%d max_rollout_len=%d must be >= 0", who, n, max_rollout_len);
+  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "%s: max_grid=%d outside [1, 16]", who, max_grid);
+  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "%s: n_max=%d outside [0, %d]", who, n_max, TOUED_MAX_OBJS);
+  const int G2 = max_grid * max_grid;
+  const int S = G2 << n_max;
+  TOUED_REQUIRE(D == nullptr || *D == S + 1, "%s: D=%d is not max_grid^2 * 2^n_max + 1 = %d", who, *D, S + 1);
+  *lds = lds_bytes(G2, n_max);
+  TOUED_REQUIRE(*lds <= kOptretLdsMax, "%s: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)", who, max_grid,
+                n_max, *lds, kOptretLdsMax);
   return 0;
 }
 
@@ -557,97 +539,47 @@ extern "C" {
 
 int toued_optimal_return(const int* levels, int n, int max_grid, int n_max, int tabular, int max_rollout_len,
                          float* v0, float* v_all, hipStream_t stream) {
-  TOUED_REQUIRE(tabular != 0, "toued_optimal_return: non-tabular environments are unsupported (the reference "
-                "raises NotImplementedError)");
-  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_optimal_return: n=%d max_rollout_len=%d must be >= 0", n,
-                max_rollout_len);
-  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_optimal_return: max_grid=%d outside [1, 16]", max_grid);
-  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_optimal_return: n_max=%d outside [0, %d]", n_max,
-                TOUED_MAX_OBJS);
-  const int G2 = max_grid * max_grid;
-  const size_t lds = optret_lds_bytes(G2, n_max);
-  TOUED_REQUIRE(lds <= kOptretLdsMax, "toued_optimal_return: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)",
-                max_grid, n_max, lds, kOptretLdsMax);
+  size_t lds;
+  if (optret_check(__func__, tabular, n, max_rollout_len, max_grid, n_max, nullptr, optret_lds_bytes, &lds)) return -1;
   if (n == 0) return 0;
-  static bool attr_set = false;
-  if (!attr_set) {
-    TOUED_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_optimal_return),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOptretLdsMax) == hipSuccess,
-                  "toued_optimal_return: cannot raise the dynamic LDS limit");
-    attr_set = true;
-  }
-  // block size from the table size: one state per thread up to 1024 threads
-  const int S = G2 << n_max;
-  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
-  hipLaunchKernelGGL(k_optimal_return, dim3(n), dim3(block), lds, stream, levels, max_grid, n_max, max_rollout_len,
-                     v0, v_all);
-  TOUED_CHECK_LAUNCH();
-  return 0;
+  const int block = optret_block((max_grid * max_grid) << n_max);
+  return optret_launch<k_optimal_return>(__func__, n, block, lds, stream, levels, max_grid, n_max, max_rollout_len,
+                                         v0, v_all);
 }
 
 int toued_policy_return(const int* levels, const float* theta, int n, int D, int max_grid, int n_max, int tabular,
                         int max_rollout_len, float* v0, float* v_all, hipStream_t stream) {
-  TOUED_REQUIRE(tabular != 0, "toued_policy_return: non-tabular environments are unsupported (the agent is not a "
-                "table over the environment's states)");
-  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_policy_return: n=%d max_rollout_len=%d must be >= 0", n,
-                max_rollout_len);
-  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_policy_return: max_grid=%d outside [1, 16]", max_grid);
-  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_policy_return: n_max=%d outside [0, %d]", n_max,
-                TOUED_MAX_OBJS);
-  const int G2 = max_grid * max_grid;
-  const int S = G2 << n_max;
-  TOUED_REQUIRE(D == S + 1, "toued_policy_return: D=%d is not max_grid^2 * 2^n_max + 1 = %d", D, S + 1);
-  const size_t lds = optret_lds_bytes(G2, n_max);
-  TOUED_REQUIRE(lds <= kOptretLdsMax, "toued_policy_return: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)",
-                max_grid, n_max, lds, kOptretLdsMax);
+  const char* const who = __func__;
+  size_t lds;
+  if (optret_check(who, tabular, n, max_rollout_len, max_grid, n_max, &D, optret_lds_bytes, &lds)) return -1;
   if (n == 0) return 0;
-  // k_optimal_return's block size; the kernel is instantiated for the work items a thread can then own, and once
-  // more for the tables past six items per thread
-  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
-  const int items = (S + block - 1) / block;
-#define TOUED_POLRET_LAUNCH(I, MORE) \
-  launch_policy_return<I, MORE>(n, block, lds, stream, levels, theta, D, max_grid, n_max, max_rollout_len, v0, v_all)
-  if (items <= 1) return TOUED_POLRET_LAUNCH(1, false);
-  if (items <= 2) return TOUED_POLRET_LAUNCH(2, false);
-  if (items <= 4) return TOUED_POLRET_LAUNCH(4, false);
-  if (items <= 6) return TOUED_POLRET_LAUNCH(6, false);      // every mode's table
-  return TOUED_POLRET_LAUNCH(4, true);
-#undef TOUED_POLRET_LAUNCH
+  // the kernel is instantiated for the work items a thread can own at k_optimal_return's block size, and once more
+  // for the tables past six items per thread
+  const int S = D - 1, block = optret_block(S), items = (S + block - 1) / block;
+  const auto launch = [&](auto I, auto more) {
+    return optret_launch<k_policy_return<decltype(I)::value, decltype(more)::value>>(
+        who, n, block, lds, stream, levels, theta, D, max_grid, n_max, max_rollout_len, v0, v_all);
+  };
+  if (items <= 6) return by_items(items, [&](auto I) { return launch(I, std::false_type{}); });      // every mode
+  return launch(std::integral_constant<int, 4>{}, std::true_type{});
 }
 
 int toued_policy_return_moments(const int* levels, const float* theta, int n, int D, int max_grid, int n_max,
                                 int tabular, int max_rollout_len, float* v0, float* var0, float* v_all,
                                 float* var_all, hipStream_t stream) {
-  TOUED_REQUIRE(tabular != 0, "toued_policy_return_moments: non-tabular environments are unsupported (the agent is "
-                "not a table over the environment's states)");
-  TOUED_REQUIRE(n >= 0 && max_rollout_len >= 0, "toued_policy_return_moments: n=%d max_rollout_len=%d must be >= 0",
-                n, max_rollout_len);
-  TOUED_REQUIRE(max_grid >= 1 && max_grid <= 16, "toued_policy_return_moments: max_grid=%d outside [1, 16]",
-                max_grid);
-  TOUED_REQUIRE(n_max >= 0 && n_max <= TOUED_MAX_OBJS, "toued_policy_return_moments: n_max=%d outside [0, %d]", n_max,
-                TOUED_MAX_OBJS);
-  const int G2 = max_grid * max_grid;
-  const int S = G2 << n_max;
-  TOUED_REQUIRE(D == S + 1, "toued_policy_return_moments: D=%d is not max_grid^2 * 2^n_max + 1 = %d", D, S + 1);
   // the f32 variance tables come on top of toued_policy_return's LDS: the limit on the table size is lower here
-  const size_t lds = polmom_lds_bytes(G2, n_max);
-  TOUED_REQUIRE(lds <= kOptretLdsMax,
-                "toued_policy_return_moments: max_grid=%d n_max=%d needs %zu bytes of LDS (limit %zu)", max_grid,
-                n_max, lds, kOptretLdsMax);
+  const char* const who = __func__;
+  size_t lds;
+  if (optret_check(who, tabular, n, max_rollout_len, max_grid, n_max, &D, polmom_lds_bytes, &lds)) return -1;
   if (n == 0) return 0;
   // toued_policy_return's block size and items per thread; a table that fits the LDS has at most six
-  const int block = S <= 64 ? 64 : (S <= 256 ? 256 : (S <= 1024 ? 512 : 1024));
-  const int items = (S + block - 1) / block;
-  TOUED_REQUIRE(items <= 6, "toued_policy_return_moments: max_grid=%d n_max=%d has %d states per thread (limit 6)",
-                max_grid, n_max, items);
-#define TOUED_POLMOM_LAUNCH(I)                                                                                     \
-  launch_policy_moments<I>(n, block, lds, stream, levels, theta, D, max_grid, n_max, max_rollout_len, v0, var0, \
-                           v_all, var_all)
-  if (items <= 1) return TOUED_POLMOM_LAUNCH(1);
-  if (items <= 2) return TOUED_POLMOM_LAUNCH(2);
-  if (items <= 4) return TOUED_POLMOM_LAUNCH(4);
-  return TOUED_POLMOM_LAUNCH(6);
-#undef TOUED_POLMOM_LAUNCH
+  const int S = D - 1, block = optret_block(S), items = (S + block - 1) / block;
+  TOUED_REQUIRE(items <= 6, "%s: max_grid=%d n_max=%d has %d states per thread (limit 6)", who, max_grid, n_max,
+                items);
+  return by_items(items, [&](auto I) {
+    return optret_launch<k_policy_moments<decltype(I)::value>>(who, n, block, lds, stream, levels, theta, D, max_grid,
+                                                               n_max, max_rollout_len, v0, var0, v_all, var_all);
+  });
 }
 
 }  // extern "C"

@@ -201,17 +201,7 @@ class RolloutWrapper:
         S = obs_dim - 1 table states (the reference's shape: the observation's last entry is the time feature, not
         a state), v_t of every tabular state, -inf at the invalid ones and 0 from max_steps_in_episode on.  A single
         level [80] returns a 0-d tensor, or [max_rollout_len, S].  Non-tabular modes raise NotImplementedError."""
-        if not self.spec.tabular:
-            raise NotImplementedError("Optimal return not implemented for non-tabular environments.")
-        if levels.dim() == 1:
-            return self.optimal_return(levels.view(1, -1), max_rollout_len, return_all)[0]
-        n, L = levels.shape[0], int(max_rollout_len)
-        S = self.obs_dim - 1
-        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
-        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
-        _lib.call("toued_optimal_return", _lib.ptr(levels), n, self.spec.max_grid_size, self.spec.max_n_objs,
-                  int(self.spec.tabular), L, _lib.ptr(v0), _lib.ptr(v_all), _lib.stream_ptr())
-        return v_all if return_all else v0
+        return self._exact_returns("optimal_return", "Optimal return", levels, None, max_rollout_len, return_all, 1)[0]
 
     def policy_return(self, levels: torch.Tensor, theta: torch.Tensor, max_rollout_len: int,
                       return_all: bool = False) -> torch.Tensor:
@@ -223,22 +213,7 @@ class RolloutWrapper:
         levels int32 [n, 80], theta f32 [n, obs_dim, 5] -> f32 [n]; ``return_all``: f32 [n, max_rollout_len, S] with
         S = obs_dim - 1, the masks of ``optimal_return``'s table.  A single level [80] with theta [obs_dim, 5] returns
         a 0-d tensor, or [max_rollout_len, S].  Non-tabular modes raise NotImplementedError."""
-        if not self.spec.tabular:
-            raise NotImplementedError("Policy return not implemented for non-tabular environments.")
-        if levels.dim() == 1:
-            return self.policy_return(levels.view(1, -1), theta.unsqueeze(0), max_rollout_len, return_all)[0]
-        n, L = levels.shape[0], int(max_rollout_len)
-        if tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32 \
-                or theta.device != levels.device:
-            raise ValueError(f"policy_return: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, expected "
-                             f"float32 {(n, self.obs_dim, 5)} on {levels.device}")
-        S = self.obs_dim - 1
-        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
-        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
-        _lib.call("toued_policy_return", _lib.ptr(levels), _lib.ptr(theta), n, self.obs_dim,
-                  self.spec.max_grid_size, self.spec.max_n_objs, int(self.spec.tabular), L, _lib.ptr(v0),
-                  _lib.ptr(v_all), _lib.stream_ptr())
-        return v_all if return_all else v0
+        return self._exact_returns("policy_return", "Policy return", levels, theta, max_rollout_len, return_all, 1)[0]
 
     def policy_return_moments(self, levels: torch.Tensor, theta: torch.Tensor, max_rollout_len: int,
                               return_all: bool = False):
@@ -250,25 +225,33 @@ class RolloutWrapper:
         return.  It is not clamped: a zero variance may come out a rounding below zero.  Not in the reference.
 
         Shapes, the single-agent form and the errors are ``policy_return``'s, for each of the two results."""
+        return tuple(self._exact_returns("policy_return_moments", "Policy return moments", levels, theta,
+                                         max_rollout_len, return_all, 2))
+
+    def _exact_returns(self, name: str, title: str, levels: torch.Tensor, theta: torch.Tensor | None,
+                       max_rollout_len: int, return_all: bool, n_out: int) -> list:
+        """optimal_return (``theta`` None), policy_return and policy_return_moments through their entry point
+        toued_<name>: the tabular check, the single-level form, theta's validation, the outputs and the call.  The
+        ``n_out`` results: v_0 (then var_0) f32 [n], or with ``return_all`` the tables f32 [n, max_rollout_len, S]."""
         if not self.spec.tabular:
-            raise NotImplementedError("Policy return moments not implemented for non-tabular environments.")
+            raise NotImplementedError(f"{title} not implemented for non-tabular environments.")
         if levels.dim() == 1:
-            m, v = self.policy_return_moments(levels.view(1, -1), theta.unsqueeze(0), max_rollout_len, return_all)
-            return m[0], v[0]
+            outs = self._exact_returns(name, title, levels.view(1, -1), None if theta is None else theta.unsqueeze(0),
+                                       max_rollout_len, return_all, n_out)
+            return [o[0] for o in outs]
         n, L = levels.shape[0], int(max_rollout_len)
-        if tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32 \
-                or theta.device != levels.device:
-            raise ValueError(f"policy_return_moments: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, "
-                             f"expected float32 {(n, self.obs_dim, 5)} on {levels.device}")
+        if theta is not None and (tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32
+                                  or theta.device != levels.device):
+            raise ValueError(f"{name}: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, expected "
+                             f"float32 {(n, self.obs_dim, 5)} on {levels.device}")
         S = self.obs_dim - 1
-        v0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
-        var0 = torch.zeros(n, dtype=torch.float32, device=levels.device)
-        v_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
-        var_all = torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
-        _lib.call("toued_policy_return_moments", _lib.ptr(levels), _lib.ptr(theta), n, self.obs_dim,
-                  self.spec.max_grid_size, self.spec.max_n_objs, int(self.spec.tabular), L, _lib.ptr(v0),
-                  _lib.ptr(var0), _lib.ptr(v_all), _lib.ptr(var_all), _lib.stream_ptr())
-        return (v_all, var_all) if return_all else (v0, var0)
+        v0 = [torch.zeros(n, dtype=torch.float32, device=levels.device) for _ in range(n_out)]
+        v_all = [torch.empty((n, L, S), dtype=torch.float32, device=levels.device) if return_all else None
+                 for _ in range(n_out)]
+        th, d = ([], []) if theta is None else ([_lib.ptr(theta)], [self.obs_dim])     # the arguments a theta adds
+        _lib.call("toued_" + name, _lib.ptr(levels), *th, n, *d, self.spec.max_grid_size, self.spec.max_n_objs,
+                  int(self.spec.tabular), L, *map(_lib.ptr, v0), *map(_lib.ptr, v_all), _lib.stream_ptr())
+        return v_all if return_all else v0
 
     def value_loss_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float, gae_lambda: float,
                           return_adv: bool = False):

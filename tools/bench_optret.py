@@ -10,7 +10,8 @@
     with alg_regret, timed the way bench.py's workload_c3 times it (a host clock around `rounds` rounds ending in a
     device synchronise, after one warm-up round), the two alternated.
 
-Prints one JSON line."""
+Prints one JSON line.  tools/bench_polret.py and tools/bench_polvar.py take their levels, tables, timing and regret
+rounds from here."""
 import argparse
 import json
 import sys
@@ -34,21 +35,38 @@ def updates_per_level(levels: np.ndarray, spec, L: int) -> np.ndarray:
     return ncell * 5 * 3 ** levels[:, L_NOBJS].astype(np.int64) * H
 
 
-def time_optimal_return(mode: str, n: int, L: int, reps: int) -> dict:
+def timed(fn, reps: int) -> float:
+    """ms per call: device events around `reps` back-to-back calls."""
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    for _ in range(reps):
+        fn()
+    ev1.record()
+    torch.cuda.synchronize()
+    return ev0.elapsed_time(ev1) / reps
+
+
+def levels_and_tables(mode: str, n: int, L: int, tables: bool = True):
+    """The wrapper, n generated levels and (``tables``) the agents' tables from create_agents scaled by 10 (the
+    regret tests' tables) of one timed shape; the keys depend on n + L."""
     from toued import prng
+    from toued.agents import create_agents
     from toued.env import LevelGenerator
     from toued.rollout import RolloutWrapper
     ro = RolloutWrapper(mode, 20)
     levels = LevelGenerator(mode)(prng.split(prng.PRNGKey(n + L, "cuda"), n))
-    ro.optimal_return(levels, L)            # warm-up: code object, LDS attribute
+    if not tables:
+        return ro, levels, None
+    theta, _ = create_agents(prng.split(prng.PRNGKey(n + L + 1, "cuda"), n), ro.obs_dim, 8)
+    theta.mul_(10.0)
+    return ro, levels, theta
+
+
+def time_optimal_return(mode: str, n: int, L: int, reps: int) -> dict:
+    ro, levels, _ = levels_and_tables(mode, n, L, tables=False)
+    v = ro.optimal_return(levels, L)        # warm-up: code object, LDS attribute
     torch.cuda.synchronize()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(reps):
-        v = ro.optimal_return(levels, L)
-    ev1.record()
-    torch.cuda.synchronize()
-    ms = ev0.elapsed_time(ev1) / reps
+    ms = timed(lambda: ro.optimal_return(levels, L), reps)
     upd = updates_per_level(levels.cpu().numpy(), ro.spec, L)
     return {"mode": mode, "levels": n, "L": L, "ms": round(ms, 3), "updates_total": int(upd.sum()),
             "updates_per_level_mean": float(upd.mean()), "updates_per_level_max": int(upd.max()),
@@ -57,32 +75,32 @@ def time_optimal_return(mode: str, n: int, L: int, reps: int) -> dict:
             "v0_mean": round(float(v.mean()), 6)}
 
 
-def regret_rounds(rounds: int) -> dict:
+def regret_rounds(rounds: int, variants: dict) -> dict:
+    """The C3 regret round (all_shortlife, 512 agents, every agent terminated) of each variant, name -> its extra
+    command-line flags: a host clock around `rounds` rounds ending in a device synchronise, after one warm-up round,
+    the variants alternated, twice."""
     from toued.env import L_LIFETIME
     from toued.parse_args import parse_args
     from toued.train import Trainer
-    trs = {}
-    for sf in ("alg_regret", "optimal_regret"):
-        args = parse_args(["--env_mode", "all_shortlife", "--num_agents", "512", "--num_mini_batches", "1",
-                           "--score_function", sf])
-        trs[sf] = Trainer(args)
+    trs = {k: Trainer(parse_args(["--env_mode", "all_shortlife", "--num_agents", "512", "--num_mini_batches", "1"]
+                                 + flags)) for k, flags in variants.items()}
 
     def one_round(tr):
         tr.agents.step = tr.agents.levels[:, L_LIFETIME].clone()     # every agent terminated: all are scored
         tr.buffer, tr.agents = tr.sampler.sample(tr.rng, tr.buffer, tr.agents)
 
-    times = {sf: [] for sf in trs}
-    for sf, tr in trs.items():
+    times = {k: [] for k in trs}
+    for tr in trs.values():
         one_round(tr)                                                  # warm-up
     for _ in range(2):                                                 # alternated
-        for sf, tr in trs.items():
+        for k, tr in trs.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(rounds):
                 one_round(tr)
             torch.cuda.synchronize()
-            times[sf].append((time.perf_counter() - t0) / rounds * 1e3)
-    return {sf: {"regret_round_ms": [round(x, 3) for x in v]} for sf, v in times.items()}
+            times[k].append((time.perf_counter() - t0) / rounds * 1e3)
+    return {k: {"regret_round_ms": [round(x, 3) for x in v]} for k, v in times.items()}
 
 
 def main():
@@ -96,7 +114,8 @@ def main():
     out = {"optimal_return": [time_optimal_return("all", 512, 750, a.reps),
                               time_optimal_return("all", 4000, 750, a.reps),
                               time_optimal_return("tabular", 512, 2000, a.reps)],
-           "c3_regret_round": regret_rounds(a.rounds)}
+           "c3_regret_round": regret_rounds(a.rounds, {sf: ["--score_function", sf]
+                                                       for sf in ("alg_regret", "optimal_regret")})}
     line = json.dumps(out)
     print(line, flush=True)
     if a.out:

@@ -17,7 +17,6 @@ import argparse
 import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -25,36 +24,19 @@ sys.path.insert(0, str(ROOT / "to-ued_amd"))
 sys.path.insert(0, str(ROOT / "tools"))
 import torch  # noqa: E402
 
-from bench_optret import updates_per_level  # noqa: E402
-
-
-def _timed(fn, reps: int) -> float:
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(reps):
-        fn()
-    ev1.record()
-    torch.cuda.synchronize()
-    return ev0.elapsed_time(ev1) / reps
+from bench_optret import levels_and_tables, regret_rounds, timed, updates_per_level  # noqa: E402
 
 
 def time_policy_return(mode: str, n: int, L: int, reps: int, trials: int) -> dict:
-    from toued import prng
-    from toued.agents import create_agents
-    from toued.env import LevelGenerator
-    from toued.rollout import RolloutWrapper
-    ro = RolloutWrapper(mode, 20)
-    levels = LevelGenerator(mode)(prng.split(prng.PRNGKey(n + L, "cuda"), n))
-    theta, _ = create_agents(prng.split(prng.PRNGKey(n + L + 1, "cuda"), n), ro.obs_dim, 8)
-    theta.mul_(10.0)
+    ro, levels, theta = levels_and_tables(mode, n, L)
     pol = lambda: ro.policy_return(levels, theta, L)
     opt = lambda: ro.optimal_return(levels, L)
     vpi, vst = pol(), opt()                  # warm-up: code objects, LDS attributes
     torch.cuda.synchronize()
     t_pol, t_opt = [], []
     for _ in range(trials):
-        t_pol.append(_timed(pol, reps))
-        t_opt.append(_timed(opt, reps))
+        t_pol.append(timed(pol, reps))
+        t_opt.append(timed(opt, reps))
     m_pol, m_opt = statistics.median(t_pol), statistics.median(t_opt)
     upd = updates_per_level(levels.cpu().numpy(), ro.spec, L)
     return {"mode": mode, "levels": n, "L": L, "policy_return_ms": round(m_pol, 3),
@@ -64,35 +46,6 @@ def time_policy_return(mode: str, n: int, L: int, reps: int, trials: int) -> dic
             "policy_updates_per_sec": round(float(upd.sum()) / (m_pol * 1e-3), 1),
             "v_pi_mean": round(float(vpi.mean()), 6), "v_star_mean": round(float(vst.mean()), 6),
             "regret_min": round(float((vst - vpi).min()), 9)}
-
-
-def regret_rounds(rounds: int) -> dict:
-    from toued.env import L_LIFETIME
-    from toued.parse_args import parse_args
-    from toued.train import Trainer
-    trs = {}
-    for sf in ("optimal_regret", "alg_regret"):
-        for ev in ("sampled", "exact"):
-            args = parse_args(["--env_mode", "all_shortlife", "--num_agents", "512", "--num_mini_batches", "1",
-                               "--score_function", sf, "--regret_eval", ev])
-            trs[f"{sf}_{ev}"] = Trainer(args)
-
-    def one_round(tr):
-        tr.agents.step = tr.agents.levels[:, L_LIFETIME].clone()     # every agent terminated: all are scored
-        tr.buffer, tr.agents = tr.sampler.sample(tr.rng, tr.buffer, tr.agents)
-
-    times = {k: [] for k in trs}
-    for tr in trs.values():
-        one_round(tr)                                                  # warm-up
-    for _ in range(2):                                                 # alternated
-        for k, tr in trs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(rounds):
-                one_round(tr)
-            torch.cuda.synchronize()
-            times[k].append((time.perf_counter() - t0) / rounds * 1e3)
-    return {k: {"regret_round_ms": [round(x, 3) for x in v]} for k, v in times.items()}
 
 
 def main():
@@ -107,7 +60,9 @@ def main():
     out = {"policy_return": [time_policy_return("all", 512, 750, a.reps, a.trials),
                              time_policy_return("all", 4000, 750, a.reps, a.trials),
                              time_policy_return("tabular", 512, 2000, a.reps, a.trials)],
-           "c3_regret_round": regret_rounds(a.rounds)}
+           "c3_regret_round": regret_rounds(a.rounds, {f"{sf}_{ev}": ["--score_function", sf, "--regret_eval", ev]
+                                                       for sf in ("optimal_regret", "alg_regret")
+                                                       for ev in ("sampled", "exact")})}
     line = json.dumps(out)
     print(line, flush=True)
     if a.out:

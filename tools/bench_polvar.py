@@ -18,7 +18,6 @@ import argparse
 import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -26,19 +25,11 @@ sys.path.insert(0, str(ROOT / "to-ued_amd"))
 sys.path.insert(0, str(ROOT / "tools"))
 import torch  # noqa: E402
 
-from bench_optret import updates_per_level  # noqa: E402
-from bench_polret import _timed  # noqa: E402
+from bench_optret import levels_and_tables, regret_rounds, timed, updates_per_level  # noqa: E402
 
 
 def time_moments(mode: str, n: int, L: int, reps: int, trials: int) -> dict:
-    from toued import prng
-    from toued.agents import create_agents
-    from toued.env import LevelGenerator
-    from toued.rollout import RolloutWrapper
-    ro = RolloutWrapper(mode, 20)
-    levels = LevelGenerator(mode)(prng.split(prng.PRNGKey(n + L, "cuda"), n))
-    theta, _ = create_agents(prng.split(prng.PRNGKey(n + L + 1, "cuda"), n), ro.obs_dim, 8)
-    theta.mul_(10.0)
+    ro, levels, theta = levels_and_tables(mode, n, L)
     mom = lambda: ro.policy_return_moments(levels, theta, L)
     pol = lambda: ro.policy_return(levels, theta, L)
     (mean, var), vpi = mom(), pol()          # warm-up: code objects, LDS attributes
@@ -47,8 +38,8 @@ def time_moments(mode: str, n: int, L: int, reps: int, trials: int) -> dict:
         raise SystemExit("bench_polvar: the moments' mean is not toued_policy_return's")
     t_mom, t_pol = [], []
     for _ in range(trials):
-        t_mom.append(_timed(mom, reps))
-        t_pol.append(_timed(pol, reps))
+        t_mom.append(timed(mom, reps))
+        t_pol.append(timed(pol, reps))
     m_mom, m_pol = statistics.median(t_mom), statistics.median(t_pol)
     upd = updates_per_level(levels.cpu().numpy(), ro.spec, L)
     return {"mode": mode, "levels": n, "L": L, "moments_ms": round(m_mom, 3), "policy_return_ms": round(m_pol, 3),
@@ -57,35 +48,6 @@ def time_moments(mode: str, n: int, L: int, reps: int, trials: int) -> dict:
             "moments_updates_per_sec": round(float(upd.sum()) / (m_mom * 1e-3), 1),
             "v_pi_mean": round(float(mean.mean()), 6), "var_mean": round(float(var.mean()), 6),
             "var_min": round(float(var.min()), 9), "var_max": round(float(var.max()), 6)}
-
-
-def regret_rounds(rounds: int) -> dict:
-    from toued.env import L_LIFETIME
-    from toued.parse_args import parse_args
-    from toued.train import Trainer
-    trs = {}
-    for name, flags in (("return_variance", ["--score_function", "return_variance"]),
-                        ("optimal_regret_sampled", ["--score_function", "optimal_regret"]),
-                        ("optimal_regret_exact", ["--score_function", "optimal_regret", "--regret_eval", "exact"])):
-        args = parse_args(["--env_mode", "all_shortlife", "--num_agents", "512", "--num_mini_batches", "1"] + flags)
-        trs[name] = Trainer(args)
-
-    def one_round(tr):
-        tr.agents.step = tr.agents.levels[:, L_LIFETIME].clone()     # every agent terminated: all are scored
-        tr.buffer, tr.agents = tr.sampler.sample(tr.rng, tr.buffer, tr.agents)
-
-    times = {k: [] for k in trs}
-    for tr in trs.values():
-        one_round(tr)                                                  # warm-up
-    for _ in range(2):                                                 # alternated
-        for k, tr in trs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(rounds):
-                one_round(tr)
-            torch.cuda.synchronize()
-            times[k].append((time.perf_counter() - t0) / rounds * 1e3)
-    return {k: {"regret_round_ms": [round(x, 3) for x in v]} for k, v in times.items()}
 
 
 def main():
@@ -100,7 +62,10 @@ def main():
     out = {"policy_return_moments": [time_moments("all", 512, 750, a.reps, a.trials),
                                      time_moments("all", 4000, 750, a.reps, a.trials),
                                      time_moments("tabular", 512, 2000, a.reps, a.trials)],
-           "c3_regret_round": regret_rounds(a.rounds)}
+           "c3_regret_round": regret_rounds(a.rounds, {
+               "return_variance": ["--score_function", "return_variance"],
+               "optimal_regret_sampled": ["--score_function", "optimal_regret"],
+               "optimal_regret_exact": ["--score_function", "optimal_regret", "--regret_eval", "exact"]})}
     line = json.dumps(out)
     print(line, flush=True)
     if a.out:
