@@ -433,6 +433,20 @@ int toued_gae(int N, int W, int T, const float* value, const float* reward, cons
 int toued_value_loss_scores(int N, int W, int T, int D, const float* vcrit, const int* tidx, const int* ttime,
                             const float* trew, const uint8_t* tdone, float gamma, float gamma_lambda, float* pvl,
                             float* l1, float* adv, hipStream_t stream);
+/* MaxMC PLR score (the maximum Monte Carlo regret estimate of Jiang et al. 2021, "Replay-Guided Adversarial
+ * Environment Design") of N agents' trajectories in toued_rollout's layout under their value critics vcrit [N][D]:
+ * score[a] = rmax_out[a] - mean over the W * T (worker, step < T) pairs of v, v the critic value of
+ * toued_value_loss_scores.  Per worker, forward in time from cum = 0, disc = 1, best = -inf: cum = cum + disc * r;
+ * disc = disc * gamma; on done best = max(best, cum), cum = 0, disc = 1; an episode still open after the last step
+ * counts with its truncated return, an empty one (done on the last step) adds nothing.  wmax[a][w] (nullable,
+ * [N][W]) = best; rmax_out[a] = max(rmax_in[a], max_w best), rmax_in (nullable = -inf everywhere, [N]) the best
+ * return the level has seen before.  Returns are discounted so that they are on the critic's scale.  f32 with one
+ * rounding per operation: wmax and rmax_out are bit-exact with the sequential restatement; the value sum is kept in
+ * f64 in a fixed order and the score rounded to f32 once: deterministic, and agent a's outputs depend on agent a's
+ * rows only.  Any W, T >= 1; 2 <= D <= 8192; W * T < 2^31. */
+int toued_max_mc_scores(int N, int W, int T, int D, const float* vcrit, const int* tidx, const int* ttime,
+                        const float* trew, const uint8_t* tdone, float gamma, const float* rmax_in, float* score,
+                        float* rmax_out, float* wmax, hipStream_t stream);
 
 /* ---- LPG reverse-time GRU on MFMA (models/lpg.py:11-35, flax GRUCell) ---- */
 size_t toued_gru_packed_floats(int which);

@@ -22,7 +22,8 @@ unpinned, no reference checkpoint exists to read back:
 = ``Level(env_params, lifetime, buffer_id)`` (util/data.py:46-51) with every ``EnvParams`` field
 (gridworld.py:21-35, per-type object tables included: the packed rows carry them), then ``score``, ``active``,
 ``new`` -- in dataclass field order, as flax's to_state_dict emits them; a buffer with stamps (--staleness_coeff > 0,
-not in the reference) appends ``stamp`` (int32 [B]) and ``clock`` (int32 scalar).  ``es_train_state_dict`` writes
+not in the reference) appends ``stamp`` (int32 [B]) and ``clock`` (int32 scalar), one with the slots' best returns
+(--score_function max_mc, not in the reference) ``max_return`` (float32 [B], -inf kept).  ``es_train_state_dict`` writes
 ``ESTrainState`` (util/data.py:63-68): ``train_state`` (the LPG TrainState, which the ES step never updates),
 ``es_params`` and ``es_state`` of evosax 0.1.4's OpenES (EvoParams / EvoState with the optimiser's
 OptParams / OptState; evosax is not installed or vendored: field names, order and defaults restated, unpinned).
@@ -189,6 +190,8 @@ def level_buffer_state_dict(buffer, spec) -> dict:
     if getattr(buffer, "stamp", None) is not None:      # --staleness_coeff > 0 (not in the reference's pytree)
         state["stamp"] = buffer.stamp.detach().cpu().numpy().astype(np.int32)
         state["clock"] = np.asarray(buffer.clock, np.int32)
+    if getattr(buffer, "max_return", None) is not None:     # --score_function max_mc (not in the reference's pytree)
+        state["max_return"] = buffer.max_return.detach().cpu().numpy().astype(np.float32)
     return state
 
 
@@ -201,8 +204,9 @@ def level_buffer_from_state_dict(state: dict, spec, device):
                          np.asarray(lv["buffer_id"]).astype(np.int32), spec)
     t = lambda a, dt: torch.as_tensor(np.array(a), dtype=dt, device=device)
     stamp = t(state["stamp"], torch.int32) if "stamp" in state else None
+    max_return = t(state["max_return"], torch.float32) if "max_return" in state else None
     return LevelBuffer(t(packed, torch.int32), t(state["score"], torch.float32), t(state["active"], torch.bool),
-                       t(state["new"], torch.bool), stamp, int(state.get("clock", 0)))
+                       t(state["new"], torch.bool), stamp, int(state.get("clock", 0)), max_return)
 
 
 _F32_MAX = float(np.finfo(np.float32).max)

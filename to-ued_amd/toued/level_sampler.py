@@ -10,7 +10,12 @@ value critic; not with --use_es, not in the reference), ``optimal_regret``
 (PLR with the true regret against the level's exact optimal return; tabular
 modes, not in the reference) and ``return_variance`` (PLR with the exact
 variance of the agent's first-episode return on the level, a learnability
-score; tabular modes, also with --use_es, not in the reference).
+score; tabular modes, also with --use_es, not in the reference) and ``max_mc``
+(PLR with MaxMC, the maximum Monte Carlo regret estimate of Robust PLR and
+ACCEL: the mean of R_max - V(s_t) over the agent's eval trajectory under its
+value critic, R_max the highest discounted episode return ever achieved on the
+level, kept per slot in ``LevelBuffer.max_return``; every env mode, not with
+--use_es, not in the reference).
 Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
@@ -41,6 +46,7 @@ from .rollout import RolloutWrapper
 SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
 MOMENT_SCORE_FUNCTIONS = ("return_variance",)   # accepted beside SCORE_FUNCTIONS: toued.plr.MOMENT_FUNCTIONS
+RETURN_SCORE_FUNCTIONS = ("max_mc",)            # accepted beside SCORE_FUNCTIONS: toued.plr.RETURN_FUNCTIONS
 SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
 TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
@@ -51,13 +57,16 @@ LEVEL_EDITORS = ("none", "accel")        # --level_editor: refill reset slots fr
 class LevelBuffer:
     """level_sampler.py:30-52: packed levels [B,64] (buffer_id packed), score, active, new.  Not in the reference:
     ``stamp`` (int32 [B], only with --staleness_coeff > 0), the round each slot was last scored or reset in, and
-    ``clock``, the number of PLR rounds the buffer has been through."""
+    ``clock``, the number of PLR rounds the buffer has been through, and ``max_return`` (f32 [B], only with
+    --score_function max_mc), the highest discounted episode return achieved on each slot's level so far, -inf where
+    there is none yet."""
     levels: torch.Tensor
     score: torch.Tensor
     active: torch.Tensor
     new: torch.Tensor
     stamp: torch.Tensor | None = None
     clock: int = 0
+    max_return: torch.Tensor | None = None
 
     def __len__(self):
         return self.score.shape[0]
@@ -96,7 +105,7 @@ class LevelSampler:
         if args.score_function in MOMENT_SCORE_FUNCTIONS and not self.spec.tabular:
             raise ValueError(f"Level score function {args.score_function} needs a tabular environment mode: the "
                              f"agent is not a table over the states of {self.env_mode}")
-        if args.score_function in VALUE_LOSS_FUNCTIONS and args.use_es:
+        if args.score_function in VALUE_LOSS_FUNCTIONS + RETURN_SCORE_FUNCTIONS and args.use_es:
             raise ValueError(f"Level score function {args.score_function} needs the agents' value critics, which "
                              f"--use_es does not train")
         self.regret_eval = getattr(args, "regret_eval", "sampled")
@@ -120,9 +129,9 @@ class LevelSampler:
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
-        if args.score_function not in SCORE_FUNCTIONS and args.score_function not in MOMENT_SCORE_FUNCTIONS:
+        if args.score_function not in SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS):
             raise ValueError(f"Level score function {args.score_function} not in known functions: "
-                             f"{SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS)}")
+                             f"{SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS)}")
         if args.score_transform not in SCORE_TRANSFORMS:
             raise ValueError(
                 f"Level score transform {args.score_transform} not in known transforms: {SCORE_TRANSFORMS}")
@@ -192,8 +201,10 @@ class LevelSampler:
         levels = self.gen(keys, buffer_ids=ids)
         B = self.buffer_size
         stamp = torch.zeros(B, dtype=torch.int32, device=self.dev) if self.staleness_coeff > 0.0 else None
+        max_return = (torch.full((B,), float("-inf"), dtype=torch.float32, device=self.dev)
+                      if self.score_function in RETURN_SCORE_FUNCTIONS else None)
         return LevelBuffer(levels, torch.zeros(B, device=self.dev), torch.zeros(B, dtype=torch.bool, device=self.dev),
-                           torch.ones(B, dtype=torch.bool, device=self.dev), stamp)
+                           torch.ones(B, dtype=torch.bool, device=self.dev), stamp, max_return=max_return)
 
     def initial_sample(self, rng, level_buffer, batch_size: int, create_value_critics_flag: bool, sl=None):
         """level_sampler.py:103-132.  ``sl`` = (lo, hi, total) agent slice of this rank."""

@@ -14,6 +14,11 @@ Additions (all default to the reference's behaviour):
                         Learnability" (Rutherford et al. 2024) for real-valued returns: no antagonist, no value critic
                         (so also with --use_es), no keys, no eval rollout; tabular modes.  The variance includes the
                         level's own randomness (termination and respawn draws), not only the policy's
+  --score_function max_mc  PLR with MaxMC, the maximum Monte Carlo regret estimate Robust PLR and ACCEL are run with
+                        (Jiang et al. 2021, "Replay-Guided Adversarial Environment Design"): the mean over the agent's
+                        eval trajectory of R_max - V(s_t) under its value critic, R_max the highest episode return ever
+                        achieved on the level (kept per buffer slot, forgotten when the slot is refilled); returns are
+                        discounted with --gamma, the critic's scale.  No antagonist, every env mode; not with --use_es
   --level_editor {none,accel}  how the PLR scores' reset round refills a freed buffer slot: ``none`` (the default) by
                         the level generator, ``accel`` with probability --edit_prob by --num_edits small edits
                         (--edit_ops: walls, objects, start, rewards; a reward moves by at most --edit_reward_delta) of a
@@ -91,7 +96,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "positive_value_loss or l1_value_loss: the mean of max(GAE, 0) or |GAE| under the agent's value "
                    "critic, not with --use_es; or optimal_regret: the true regret against the level's exact optimal "
                    "return, tabular modes; or return_variance: the exact variance of the agent's return on the level, "
-                   "tabular modes; see --regret_eval for the regret scores' agent evaluation)", type=str,
+                   "tabular modes; or max_mc: the mean of R_max - V(s_t) under the agent's value critic, R_max the "
+                   "level's best return so far, not with --use_es; see --regret_eval for the regret scores' agent "
+                   "evaluation)", type=str,
                    default="random")
     p.add_argument("--p_replay", help="Probability of replaying a level from the buffer (vs. random sampling)",
                    type=float, default=0.5)

@@ -13,6 +13,14 @@ With ``score_function = positive_value_loss`` or ``l1_value_loss`` (not in the r
 ``value_loss_scores``: one eval rollout of the LPG agent and the mean of max(GAE, 0) or |GAE| under the agent's own
 value critic (toued_value_loss_scores), no antagonist; the rest is unchanged.
 
+With ``score_function = max_mc`` (not in the reference) step 2 is ``max_mc_scores``: the same eval rollout, and
+MaxMC, the maximum Monte Carlo regret estimate of Robust PLR and ACCEL (Jiang et al. 2021, "Replay-Guided Adversarial
+Environment Design"): the mean over the trajectory of R_max - V(s_t), R_max the highest episode return ever achieved on
+the level (toued_max_mc_scores).  Returns are discounted with --gamma so that they live on the value critic's scale.
+The buffer then carries ``max_return`` (f32 [B], -inf where nothing was achieved yet): the slots' R_max is read before
+the round, written back max-combined in step 3 and forgotten (-inf) for the slots step 1 refills, edited levels
+included.  No antagonist and no tabular level: every env mode.
+
 With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
 exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
 
@@ -79,7 +87,8 @@ def parent_ids(buffer, reset_ids: torch.Tensor) -> torch.Tensor:
 
 def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: int | None = None) -> torch.Tensor:
     """level_sampler.py:331-353, in place on ``buffer``; returns the reset ids [n_new].  A buffer with stamps
-    (--staleness_coeff > 0) gets ``stamp[ids] = now``.
+    (--staleness_coeff > 0) gets ``stamp[ids] = now``, one with ``max_return`` (--score_function max_mc)
+    ``max_return[ids] = -inf``.
 
     With ``--level_editor accel`` (not in the reference) the generated levels then pass through the level editor:
     a row whose coin (``--edit_prob``) says so becomes an edited copy of a parent, a scored buffer level read before
@@ -106,6 +115,8 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: in
     buffer.new = new
     if buffer.stamp is not None and now is not None:
         buffer.stamp.index_fill_(0, il, int(now))
+    if buffer.max_return is not None:      # a refilled slot holds another level (an edited one too)
+        buffer.max_return.index_fill_(0, il, float("-inf"))
     return ids
 
 
@@ -211,11 +222,26 @@ def value_loss_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_the
     dev = keys.device
     pvl = torch.empty(n, dtype=torch.float32, device=dev)
     l1 = torch.empty(n, dtype=torch.float32, device=dev)
+    ro = sampler.rollout_manager
+    vcrit = vcrit.reshape(n, ro.obs_dim)
+    for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
+        p, l = ro.value_loss_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, sampler.args.gae_lambda)
+        pvl[lo:hi] = p
+        l1[lo:hi] = l
+    return pvl, l1
+
+
+def _eval_trajectory_chunks(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
+                            chunk_agents: int | None):
+    """The eval trajectories that the critic-based scores read, a chunk of agents at a time: yields (lo, hi,
+    Transition of agents lo..hi-1); nothing for n = 0.  The keys, reset and rollout are ``value_loss_scores``'; the
+    trajectory buffers are reused from chunk to chunk, so a chunk's Transition holds until the next one is asked
+    for."""
+    n = keys.shape[0]
     if n == 0:
-        return pvl, l1
+        return
     ro = sampler.rollout_manager
     W = sampler.env_workers
-    vcrit = vcrit.reshape(n, ro.obs_dim)
     rng, _ = _split2(keys)
     rng, _ = _split2(rng)
     lpg_rng, _ = _split2(rng)
@@ -231,10 +257,7 @@ def value_loss_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_the
             out = Transition(*(getattr(out, f)[:hi - lo] for f in ("obs_idx", "obs_time", "action", "reward", "done")))
         out, _, _ = ro.batch_rollout(ro_keys, lpg_theta[lo:hi].contiguous(), lv, state, eval=True, out=out,
                                      inplace_state=True)
-        p, l = ro.value_loss_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, sampler.args.gae_lambda)
-        pvl[lo:hi] = p
-        l1[lo:hi] = l
-    return pvl, l1
+        yield lo, hi, out
 
 
 def positive_value_loss(sampler, keys, levels, lpg_theta, vcrit) -> torch.Tensor:
@@ -247,6 +270,36 @@ def l1_value_loss(sampler, keys, levels, lpg_theta, vcrit) -> torch.Tensor:
 
 # the scores that read the agents' value critics: the regret functions' arguments plus AgentBatch.vcrit's rows
 VALUE_LOSS_FUNCTIONS = {"positive_value_loss": positive_value_loss, "l1_value_loss": l1_value_loss}
+
+
+def max_mc_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor, vcrit: torch.Tensor,
+                  prior: torch.Tensor, chunk_agents: int | None = None):
+    """The MaxMC PLR score of n LPG agents (the maximum Monte Carlo regret estimate of Jiang et al. 2021,
+    "Replay-Guided Adversarial Environment Design"): (score, rmax), f32 [n] each.  ``rmax`` = max(``prior``, the best
+    episode return of any worker on the agent's eval trajectory), ``prior`` f32 [n] the best return the agent's level
+    has seen so far (LevelBuffer.max_return of its slot, -inf for a level never scored); ``score`` = rmax - the mean
+    of the value critic ``vcrit`` [n, obs_dim] over the trajectory, the unclipped mean of R_max - V(s_t).  Returns are
+    discounted with the sampler's --gamma so that they live on the value critic's scale; the episode still open at
+    the trajectory's end counts with its truncated return (RolloutWrapper.max_mc_scores).  No antagonist and no
+    tabular level: any env mode.  The keys, the eval trajectory and the chunking are ``value_loss_scores``', so the
+    scored trajectory is the one the other scores use, and the chunking changes no bit.  An extension: the reference's
+    LevelSampler has no such score."""
+    n = keys.shape[0]
+    dev = keys.device
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    rmax = torch.empty(n, dtype=torch.float32, device=dev)
+    ro = sampler.rollout_manager
+    vcrit = vcrit.reshape(n, ro.obs_dim)
+    for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
+        s, r = ro.max_mc_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, prior[lo:hi].contiguous())
+        score[lo:hi] = s
+        rmax[lo:hi] = r
+    return score, rmax
+
+
+# the scores from the returns of the agent's eval trajectory, remembered per buffer slot: the value-loss functions'
+# arguments plus the slots' LevelBuffer.max_return; they return (score, the slots' new max_return)
+RETURN_FUNCTIONS = {"max_mc": max_mc_scores}
 
 
 # the regret round's eval draws ([eval_len][2n * W][4] u32, plus as much key-chain scratch) are made ahead when they fit
@@ -298,8 +351,9 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     """Returns (rng, buffer, new_levels [n_local, 64]) — new_levels for terminated agents, the
     caller keeps the old level elsewhere (``term_mask_fn``)."""
     world = sampler.world
+    return_fn = RETURN_FUNCTIONS.get(sampler.score_function)
     value_loss = VALUE_LOSS_FUNCTIONS.get(sampler.score_function)
-    if value_loss is not None and agents.vcrit is None:
+    if (value_loss is not None or return_fn is not None) and agents.vcrit is None:
         raise ValueError(f"Level score function {sampler.score_function} needs the agents' value critics "
                          f"(AgentBatch.vcrit is None)")
     N = agents.n if sl is None else sl[2]
@@ -312,6 +366,15 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     side = getattr(sampler, "_plr_side", None)
     if side is None:
         side = sampler._plr_side = torch.cuda.Stream(device=dev)
+    prior = rmax = None
+    if return_fn is not None:
+        if buffer.max_return is None:
+            raise ValueError(f"Level score function {sampler.score_function} needs a level buffer with max_return "
+                             f"(LevelSampler.initialize_buffer makes it; a checkpoint written without it has none)")
+        # the slots' best returns so far, read on the main stream before the side stream is let go: its reset of
+        # other slots' max_return can then never race this read
+        prior = buffer.max_return[agents.levels[:, L_BUFID].long()]
+        rmax = torch.full((agents.n,), float("-inf"), dtype=torch.float32, device=dev)
     side.wait_stream(main)
     # the side kernels read `sub` and the old `buffer.new` (both from main's allocator pool) after this function has
     # dropped them: keep their blocks from being reused by main until the side stream's work has passed them
@@ -328,6 +391,12 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     if value_loss is not None:
         vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
         regret = lambda s, k, lv, th, sel=slice(None): value_loss(s, k, lv, th, vcrit[sel].contiguous())
+    elif return_fn is not None:
+        vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
+
+        def regret(s, k, lv, th, sel=slice(None)):
+            sc, rmax[sel] = return_fn(s, k, lv, th, vcrit[sel].contiguous(), prior[sel].contiguous())
+            return sc
     else:
         score_fn = REGRET_FUNCTIONS.get(sampler.score_function) or MOMENT_FUNCTIONS[sampler.score_function]
         regret = lambda s, k, lv, th, sel=None: score_fn(s, k, lv, th)
@@ -344,8 +413,9 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
         term_g = world.all_gather_cat(term.to(torch.int32)).bool()
         score_g = world.all_gather_cat(score)
         old_g = world.all_gather_cat(old_ids)
+        rmax_g = world.all_gather_cat(rmax) if rmax is not None else None
     else:
-        term_g, score_g, old_g = term, score, old_ids
+        term_g, score_g, old_g, rmax_g = term, score, old_ids, rmax
     main.wait_stream(side)
     buffer.new.record_stream(main)     # allocated on the side stream
     # buffer update for terminated levels (:188-200), without a boolean-mask gather (a host sync that would hold the
@@ -357,6 +427,10 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     _scatter_into(buffer.new, t_ids, False)
     if buffer.stamp is not None:       # the gathered ids: every rank's copy stays identical
         _scatter_into(buffer.stamp, t_ids, now)
+    if rmax_g is not None:             # max-combined: two agents on one slot cannot lose the larger return
+        ext = torch.cat([buffer.max_return, buffer.max_return.new_full((1,), float("-inf"))])
+        ext.scatter_reduce_(0, t_ids, rmax_g, "amax", include_self=True)
+        buffer.max_return.copy_(ext[:-1])
     # replay vs random (:203-227)
     ks = prng.split(rng, 3)                           # rng, replay_rng, random_rng
     kbuf = torch.stack([ks[1], ks[2], ks[0]]).contiguous()

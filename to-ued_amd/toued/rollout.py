@@ -277,6 +277,36 @@ class RolloutWrapper:
                   gl, _lib.ptr(pvl), _lib.ptr(l1), _lib.ptr(adv), _lib.stream_ptr())
         return (pvl, l1, adv) if return_adv else (pvl, l1)
 
+    def max_mc_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float,
+                      rmax_in: torch.Tensor | None = None, return_worker_max: bool = False):
+        """The MaxMC PLR score of N agents' trajectories under their value critics ``vcrit`` f32 [N, D] or [N, D, 1]
+        (toued_max_mc_scores: value gather, per-worker returns and the mean in one launch, no host synchronisation):
+        (score, rmax), f32 [N] each.  ``rmax`` = max(``rmax_in``, the best episode return of any worker), ``rmax_in``
+        f32 [N] the best return each level has seen before (None: -inf); ``score`` = rmax - mean of V(s_t) over
+        workers and steps, the unclipped mean of R_max - V(s_t) (Jiang et al. 2021, "Replay-Guided Adversarial
+        Environment Design").  Returns are discounted with ``gamma`` so that they live on the value critic's scale;
+        the episode still open at the trajectory's end counts with its truncated return.  ``return_worker_max``: also
+        each worker's best return, f32 [N, W]."""
+        N, T, W = transition.reward.shape
+        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
+                or transition.done.shape != (N, T, W):
+            raise ValueError(f"max_mc_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
+                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
+        vcrit = vcrit.reshape(N, vcrit.shape[1]).contiguous()     # [N, D] or the critic table [N, D, 1]
+        dev = transition.reward.device
+        if rmax_in is not None:
+            if rmax_in.shape != (N,) or rmax_in.dtype != torch.float32 or rmax_in.device != dev:
+                raise ValueError(f"max_mc_scores: rmax_in {rmax_in.dtype} {tuple(rmax_in.shape)} on {rmax_in.device}, "
+                                 f"expected float32 {(N,)} on {dev}")
+            rmax_in = rmax_in.contiguous()
+        score = torch.empty(N, dtype=torch.float32, device=dev)
+        rmax = torch.empty(N, dtype=torch.float32, device=dev)
+        wmax = torch.empty((N, W), dtype=torch.float32, device=dev) if return_worker_max else None
+        _lib.call("toued_max_mc_scores", N, W, T, vcrit.shape[1], _lib.ptr(vcrit), _lib.ptr(transition.obs_idx),
+                  _lib.ptr(transition.obs_time), _lib.ptr(transition.reward), _lib.ptr(transition.done), float(gamma),
+                  _lib.ptr(rmax_in), _lib.ptr(score), _lib.ptr(rmax), _lib.ptr(wmax), _lib.stream_ptr())
+        return (score, rmax, wmax) if return_worker_max else (score, rmax)
+
     def eval_returns(self, agent_keys: torch.Tensor, theta: torch.Tensor, levels: torch.Tensor,
                      state: torch.Tensor) -> torch.Tensor:
         """batch_rollout(..., eval=True) when only cum_return is consumed (eval_agent): returns-only

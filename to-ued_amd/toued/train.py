@@ -69,7 +69,8 @@ class Trainer:
             from .level_sampler import LevelBuffer
             b = self.buffer
             self.buffer_init = LevelBuffer(b.levels.clone(), b.score.clone(), b.active.clone(), b.new.clone(),
-                                           None if b.stamp is None else b.stamp.clone(), b.clock)
+                                           None if b.stamp is None else b.stamp.clone(), b.clock,
+                                           None if b.max_return is None else b.max_return.clone())
         if args.use_es:
             from .es import ESTrainStep
             self.step_fn = ESTrainStep(args, self.sampler, n_local, self.eta, self.dev, self.world)
