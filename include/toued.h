@@ -447,6 +447,20 @@ int toued_value_loss_scores(int N, int W, int T, int D, const float* vcrit, cons
 int toued_max_mc_scores(int N, int W, int T, int D, const float* vcrit, const int* tidx, const int* ttime,
                         const float* trew, const uint8_t* tdone, float gamma, const float* rmax_in, float* score,
                         float* rmax_out, float* wmax, hipStream_t stream);
+/* Policy PLR scores (Prioritized Level Replay's policy entropy, least confidence and min margin, Jiang et al. 2021,
+ * Table 1) of N agents' trajectories under their actor tables theta [N][D][5], on the observation rows of
+ * toued_rollout's layout (tidx / ttime [N][T+1][W]; rows t < T enter, the end observation does not, as in
+ * toued_max_mc_scores).  Per (worker, step): p = softmax(theta[a][idx] + ((float)time * 0.001f) * theta[a][D-1]) by
+ * the operations of the rollout's actor, so p is bit for bit the distribution the action was drawn from; with
+ * d_j = l_j - max l, e_j = exp(d_j), s = sum e_j: H = max(log s - (sum e_j d_j) / s, 0) (the entropy), lc = 1 - p_max,
+ * mm = 1 - (p_max - p_2nd), p_2nd the second entry of p sorted descending (two equal maxima: mm = 1).  entropy[a] =
+ * mean over the W * T pairs of H, divided by log 5; least_conf[a] = mean lc; min_margin[a] = mean mm.  Any of the three
+ * may be null (not all); steps (nullable, [N][3][T][W]) receives the per-step terms H, lc, mm.  f32 with one rounding
+ * per operation: the terms are bit-exact with the numpy restatement; the sums are kept in f64 in a fixed order and
+ * rounded to f32 once: deterministic, and agent a's scores depend on agent a's rows only.  An index outside the table
+ * is held to row D-1.  Any W, T >= 1; 2 <= D <= 7065 (the table is staged in LDS); W * T < 2^31. */
+int toued_policy_scores(int N, int W, int T, int D, const float* theta, const int* tidx, const int* ttime,
+                        float* entropy, float* least_conf, float* min_margin, float* steps, hipStream_t stream);
 
 /* ---- LPG reverse-time GRU on MFMA (models/lpg.py:11-35, flax GRUCell) ---- */
 size_t toued_gru_packed_floats(int which);

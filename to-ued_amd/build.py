@@ -26,8 +26,11 @@ ARCH = os.environ.get("TOUED_ARCH", "gfx950")
 
 # files allowed to contract a*b+c into fma (tolerance-checked float kernels)
 CONTRACT_OK = {"gru.hip"}
-# per-file extras: packed f32 VALU (SLP-vectorised adds) beside MFMAs costs issue cycles (MI355X_MICROARCH.md)
-EXTRA = {"wgrad.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"]}
+# per-file extras: packed f32 VALU (SLP-vectorised adds) beside MFMAs costs issue cycles (MI355X_MICROARCH.md); in
+# polscore.hip's pure-VALU loop the packed multiplies and adds the vectoriser forms across a thread's pairs cost more
+# than the scalar ones they replace
+EXTRA = {"wgrad.hip": ["-fno-slp-vectorize"], "gru.hip": ["-fno-slp-vectorize"],
+         "polscore.hip": ["-fno-slp-vectorize"]}
 
 
 def hipcc() -> str:

@@ -15,6 +15,10 @@ score; tabular modes, also with --use_es, not in the reference) and ``max_mc``
 ACCEL: the mean of R_max - V(s_t) over the agent's eval trajectory under its
 value critic, R_max the highest discounted episode return ever achieved on the
 level, kept per slot in ``LevelBuffer.max_return``; every env mode, not with
+--use_es, not in the reference) and ``policy_entropy`` / ``least_confidence`` /
+``min_margin`` (PLR with the mean over the agent's eval trajectory of its
+policy's entropy over log 5, of 1 - max pi, or of 1 - (max pi - second-largest
+pi): no critic, no antagonist, no buffer state; every env mode, also with
 --use_es, not in the reference).
 Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
@@ -47,6 +51,8 @@ SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_
 VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
 MOMENT_SCORE_FUNCTIONS = ("return_variance",)   # accepted beside SCORE_FUNCTIONS: toued.plr.MOMENT_FUNCTIONS
 RETURN_SCORE_FUNCTIONS = ("max_mc",)            # accepted beside SCORE_FUNCTIONS: toued.plr.RETURN_FUNCTIONS
+# accepted beside SCORE_FUNCTIONS: toued.plr.POLICY_FUNCTIONS
+POLICY_SCORE_FUNCTIONS = ("policy_entropy", "least_confidence", "min_margin")
 SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
 TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
@@ -129,9 +135,9 @@ class LevelSampler:
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
-        if args.score_function not in SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS):
-            raise ValueError(f"Level score function {args.score_function} not in known functions: "
-                             f"{SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS)}")
+        known = SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS + POLICY_SCORE_FUNCTIONS)
+        if args.score_function not in known:
+            raise ValueError(f"Level score function {args.score_function} not in known functions: {known}")
         if args.score_transform not in SCORE_TRANSFORMS:
             raise ValueError(
                 f"Level score transform {args.score_transform} not in known transforms: {SCORE_TRANSFORMS}")

@@ -19,6 +19,11 @@ Additions (all default to the reference's behaviour):
                         eval trajectory of R_max - V(s_t) under its value critic, R_max the highest episode return ever
                         achieved on the level (kept per buffer slot, forgotten when the slot is refilled); returns are
                         discounted with --gamma, the critic's scale.  No antagonist, every env mode; not with --use_es
+  --score_function policy_entropy | least_confidence | min_margin  PLR with the scores that read nothing but the
+                        agent's own policy (Jiang et al. 2021, "Prioritized Level Replay", Table 1): the mean over the
+                        agent's eval trajectory of the policy entropy -sum_a pi log pi divided by log 5 (its maximum),
+                        of the least confidence 1 - max_a pi, or of the min margin 1 - (max_a pi - second-largest_a pi).
+                        No antagonist, no value critic (so also with --use_es), no buffer state; every env mode
   --level_editor {none,accel}  how the PLR scores' reset round refills a freed buffer slot: ``none`` (the default) by
                         the level generator, ``accel`` with probability --edit_prob by --num_edits small edits
                         (--edit_ops: walls, objects, start, rewards; a reward moves by at most --edit_reward_delta) of a
@@ -97,7 +102,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "critic, not with --use_es; or optimal_regret: the true regret against the level's exact optimal "
                    "return, tabular modes; or return_variance: the exact variance of the agent's return on the level, "
                    "tabular modes; or max_mc: the mean of R_max - V(s_t) under the agent's value critic, R_max the "
-                   "level's best return so far, not with --use_es; see --regret_eval for the regret scores' agent "
+                   "level's best return so far, not with --use_es; or policy_entropy, least_confidence or min_margin: "
+                   "the mean over the agent's eval trajectory of its policy's entropy over log 5, of 1 - max pi, or "
+                   "of 1 - (max pi - second-largest pi), no critic, also with --use_es; see --regret_eval for the regret scores' agent "
                    "evaluation)", type=str,
                    default="random")
     p.add_argument("--p_replay", help="Probability of replaying a level from the buffer (vs. random sampling)",

@@ -21,6 +21,12 @@ The buffer then carries ``max_return`` (f32 [B], -inf where nothing was achieved
 the round, written back max-combined in step 3 and forgotten (-inf) for the slots step 1 refills, edited levels
 included.  No antagonist and no tabular level: every env mode.
 
+With ``score_function = policy_entropy``, ``least_confidence`` or ``min_margin`` (not in the reference) step 2 is
+``policy_scores``: the same eval rollout, and the mean over the trajectory of the policy entropy (over log 5), of
+1 - max pi or of 1 - (max pi - second-largest pi), the three scores of Prioritized Level Replay (Jiang et al. 2021,
+Table 1) that read nothing but the agent's own policy (toued_policy_scores).  No antagonist, no value critic (so also
+with --use_es), no tabular level and no buffer state: every env mode; the rest is unchanged.
+
 With ``score_function = optimal_regret`` (tabular modes; not in the reference) step 2 is ``optimal_regret``: the
 exact optimal return of the level (toued_optimal_return) minus eval(LPG), no antagonist; the rest is unchanged.
 
@@ -302,6 +308,43 @@ def max_mc_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: 
 RETURN_FUNCTIONS = {"max_mc": max_mc_scores}
 
 
+def policy_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
+                  chunk_agents: int | None = None):
+    """The policy PLR scores of n LPG agents (Prioritized Level Replay, Jiang et al. 2021, Table 1): (policy entropy,
+    least confidence, min margin), f32 [n] each, the means over the agent's eval trajectory (``env_workers`` workers,
+    ``eval_rollout_len`` steps) of the entropy of its policy divided by log 5, of 1 - max pi and of
+    1 - (max pi - second-largest pi) (RolloutWrapper.policy_scores).  They read the agent's actor table and the
+    observations it visited, nothing else: no antagonist, no value critic (so also with --use_es), no tabular level
+    and no buffer state.  The keys, the eval trajectory and the chunking are ``value_loss_scores``', so the scored
+    trajectory is the one the other scores use, and the chunking changes no bit.  An extension: the reference's
+    LevelSampler has no such score."""
+    n = keys.shape[0]
+    dev = keys.device
+    ent = torch.empty(n, dtype=torch.float32, device=dev)
+    lc = torch.empty(n, dtype=torch.float32, device=dev)
+    mm = torch.empty(n, dtype=torch.float32, device=dev)
+    ro = sampler.rollout_manager
+    for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
+        ent[lo:hi], lc[lo:hi], mm[lo:hi] = ro.policy_scores(out, lpg_theta[lo:hi].contiguous())
+    return ent, lc, mm
+
+
+def policy_entropy(sampler, keys, levels, lpg_theta) -> torch.Tensor:
+    return policy_scores(sampler, keys, levels, lpg_theta)[0]
+
+
+def least_confidence(sampler, keys, levels, lpg_theta) -> torch.Tensor:
+    return policy_scores(sampler, keys, levels, lpg_theta)[1]
+
+
+def min_margin(sampler, keys, levels, lpg_theta) -> torch.Tensor:
+    return policy_scores(sampler, keys, levels, lpg_theta)[2]
+
+
+# the scores that read nothing but the agent's own policy on its eval trajectory: the regret functions' signature
+POLICY_FUNCTIONS = {"policy_entropy": policy_entropy, "least_confidence": least_confidence, "min_margin": min_margin}
+
+
 # the regret round's eval draws ([eval_len][2n * W][4] u32, plus as much key-chain scratch) are made ahead when they fit
 EVAL_DRAWS_MAX_BYTES = 4 << 30
 
@@ -398,7 +441,8 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
             sc, rmax[sel] = return_fn(s, k, lv, th, vcrit[sel].contiguous(), prior[sel].contiguous())
             return sc
     else:
-        score_fn = REGRET_FUNCTIONS.get(sampler.score_function) or MOMENT_FUNCTIONS[sampler.score_function]
+        score_fn = (REGRET_FUNCTIONS.get(sampler.score_function) or POLICY_FUNCTIONS.get(sampler.score_function)
+                    or MOMENT_FUNCTIONS[sampler.score_function])
         regret = lambda s, k, lv, th, sel=None: score_fn(s, k, lv, th)
     if sampler.regret_all_agents:
         score = regret(sampler, keys, agents.levels, agents.theta)

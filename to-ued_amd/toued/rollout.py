@@ -307,6 +307,34 @@ class RolloutWrapper:
                   _lib.ptr(rmax_in), _lib.ptr(score), _lib.ptr(rmax), _lib.ptr(wmax), _lib.stream_ptr())
         return (score, rmax, wmax) if return_worker_max else (score, rmax)
 
+    def policy_scores(self, transition: Transition, theta: torch.Tensor, return_steps: bool = False):
+        """The policy PLR scores of N agents' trajectories under their actor tables ``theta`` f32 [N, D, 5]
+        (toued_policy_scores: the softmax of the rollout's actor, the three terms and their means in one launch, no host
+        synchronisation): (entropy, least confidence, min margin), f32 [N] each, the means over workers and steps
+        t < T of the policy entropy (divided by log 5, its maximum), of 1 - max pi and of 1 - (max pi - second-largest
+        pi) (Prioritized Level Replay, Jiang et al. 2021, Table 1).  Only the observations are read: no reward, no
+        done flag, no value critic.  ``return_steps``: also the per-step terms f32 [N, 3, T, W] (entropy before the
+        division by log 5, least confidence, min margin)."""
+        N, T, W = transition.reward.shape
+        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
+                or transition.done.shape != (N, T, W):
+            raise ValueError(f"policy_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
+                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
+        dev = transition.reward.device
+        if theta.dim() != 3 or theta.shape[0] != N or theta.shape[2] != 5 or theta.dtype != torch.float32 \
+                or theta.device != dev:
+            raise ValueError(f"policy_scores: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, expected "
+                             f"float32 {(N, 'D', 5)} on {dev}")
+        theta = theta.contiguous()
+        ent = torch.empty(N, dtype=torch.float32, device=dev)
+        lc = torch.empty(N, dtype=torch.float32, device=dev)
+        mm = torch.empty(N, dtype=torch.float32, device=dev)
+        steps = torch.empty((N, 3, T, W), dtype=torch.float32, device=dev) if return_steps else None
+        _lib.call("toued_policy_scores", N, W, T, theta.shape[1], _lib.ptr(theta), _lib.ptr(transition.obs_idx),
+                  _lib.ptr(transition.obs_time), _lib.ptr(ent), _lib.ptr(lc), _lib.ptr(mm), _lib.ptr(steps),
+                  _lib.stream_ptr())
+        return (ent, lc, mm, steps) if return_steps else (ent, lc, mm)
+
     def eval_returns(self, agent_keys: torch.Tensor, theta: torch.Tensor, levels: torch.Tensor,
                      state: torch.Tensor) -> torch.Tensor:
         """batch_rollout(..., eval=True) when only cum_return is consumed (eval_agent): returns-only
