@@ -124,6 +124,36 @@ int toued_level_gen_masked(const void* program, const uint32_t* keys, const int*
 int toued_level_edit(const int* buffer_levels, const int* parent_ids, const uint32_t* keys, int n, int max_n_objs,
                      int max_n_types, float p_edit, int num_edits, int ops_mask, float reward_delta,
                      int* levels_inout, uint8_t* edited_out, hipStream_t stream);
+/* Level reachability statistics (ACCEL's complexity metrics, Parker-Holder et al. 2022, and the level editor's
+ * solvability test; not in the reference) of n levels [n][80], read only.  R is the closure of {start} under the
+ * environment's move _get_next_pos (gridworld.py:138-146: border clamps, then a move into a wall cell stays put) over
+ * the four moving actions, and dist(c), c in R, the fewest moves from the start to c.  The start is in R whatever its
+ * own wall bit says, wall bits at cells >= g^2 are never read, and the last cell of a row is no neighbour of the next
+ * row's first.  grid_size is held to [1, max_grid], n_objs to [0, max_n_objs] and start_pos to [0, max_grid^2 - 1]
+ * (as toued_optimal_return holds them); a start >= g^2 stays alone in R, and an object cell outside [0, g^2) is not in
+ * R: no row content causes an out-of-range access.  stats [n][TOUED_LSTAT_WORDS], int32, indexed by TOUED_LSTAT_*:
+ *   CELLS g^2; N_WALLS wall bits set at cells < g^2; N_REACH |R|; ECC max of dist over R;
+ *   N_OBJ_REACH the objects i < n_objs whose static cell is in R; N_POS_REACH those of them with reward > 0 (the
+ *   resolved per-object word); NEAREST_POS the least dist among the latter, -1 if there is none;
+ *   SOLVABLE 1 if NEAREST_POS >= 0 and max(NEAREST_POS, 1) <= max_steps_in_episode, else 0;
+ *   OBJ_DIST + i, i < TOUED_MAX_OBJS: dist of object i's static cell, -1 for i >= n_objs or a cell outside R.
+ * A row with random_respawn != 0 draws its object cells per episode: N_OBJ_REACH = N_POS_REACH = 0,
+ * NEAREST_POS = OBJ_DIST = -1 and SOLVABLE = -1 (not defined).  dist (nullable) [n][max_grid^2]: dist(c) at the cells
+ * of R below g^2, -1 everywhere else (walls, unreachable cells, cells >= g^2).  One wave per level, no atomics,
+ * run-to-run bit-identical.  -1 for negative n, max_grid outside [1, 16] (max_grid^2 > 256), max_n_objs outside
+ * [0, TOUED_MAX_OBJS], NULL levels or stats with n > 0; n == 0 succeeds. */
+#define TOUED_LSTAT_WORDS 16
+#define TOUED_LSTAT_CELLS 0
+#define TOUED_LSTAT_N_WALLS 1
+#define TOUED_LSTAT_N_REACH 2
+#define TOUED_LSTAT_ECC 3
+#define TOUED_LSTAT_N_OBJ_REACH 4
+#define TOUED_LSTAT_N_POS_REACH 5
+#define TOUED_LSTAT_NEAREST_POS 6
+#define TOUED_LSTAT_SOLVABLE 7
+#define TOUED_LSTAT_OBJ_DIST 8
+int toued_level_stats(const int* levels, int n, int max_grid, int max_n_objs, int* stats, int* dist,
+                      hipStream_t stream);
 
 /* ---- gymnax Environment plugin API (GridWorld, gridworld.py:72-211) ----
  * Worker i uses levels[i / W]; keys are per worker. */

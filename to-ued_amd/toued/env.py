@@ -11,6 +11,7 @@ int32[12, n] SoA; observations are compact (tab_idx, time) int32 pairs.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -169,13 +170,72 @@ def parse_edit_ops(ops) -> int:
     return mask
 
 
+LSTAT_WORDS = 16      # include/toued.h TOUED_LSTAT_*
+LSTAT_CELLS, LSTAT_N_WALLS, LSTAT_N_REACH, LSTAT_ECC, LSTAT_N_OBJ_REACH, LSTAT_N_POS_REACH = 0, 1, 2, 3, 4, 5
+LSTAT_NEAREST_POS, LSTAT_SOLVABLE, LSTAT_OBJ_DIST = 6, 7, 8
+
+
+class LevelStats(NamedTuple):
+    """Reachability statistics of n levels (toued_level_stats), int32 [n] each (0-d for a single level):
+    ``cells`` g^2, ``n_walls`` inside the grid, ``n_reach`` cells the agent can stand on, ``ecc`` the farthest of
+    them in moves from the start, ``n_obj_reach`` / ``n_pos_reach`` the objects / positive-reward objects among them,
+    ``nearest_pos`` the moves to the nearest positive reward (-1: none), ``solvable`` (1, 0, or -1 for a level with
+    random respawn, whose object cells are drawn per episode), ``obj_dist`` [n, max_n_objs] the moves to each object
+    (-1: unused or unreachable) and ``dist`` [n, G^2] the whole distance map (-1: wall, unreachable or outside the
+    grid), or None."""
+    cells: torch.Tensor
+    n_walls: torch.Tensor
+    n_reach: torch.Tensor
+    ecc: torch.Tensor
+    n_obj_reach: torch.Tensor
+    n_pos_reach: torch.Tensor
+    nearest_pos: torch.Tensor
+    solvable: torch.Tensor
+    obj_dist: torch.Tensor
+    dist: torch.Tensor | None
+
+
+def level_stats_raw(levels: torch.Tensor, spec: EnvSpec, dist: torch.Tensor | None = None) -> torch.Tensor:
+    """toued_level_stats on ``levels`` int32 [n, 80] on the current stream: the stats words int32 [n, 16];
+    ``dist`` (int32 [n, G^2], optional) receives the distance maps."""
+    n = levels.shape[0]
+    stats = torch.empty((n, LSTAT_WORDS), dtype=torch.int32, device=levels.device)
+    _lib.call("toued_level_stats", _lib.ptr(levels), n, spec.max_grid_size, spec.max_n_objs, _lib.ptr(stats),
+              _lib.ptr(dist), _lib.stream_ptr())
+    return stats
+
+
+def level_stats(levels: torch.Tensor, spec: EnvSpec, return_dist: bool = False) -> LevelStats:
+    """Which cells of each level the agent can reach from its start, how far they are, and whether a positive reward
+    lies within ``max_steps_in_episode`` moves (toued_level_stats; one launch on the current stream, no host
+    synchronisation): ACCEL's complexity metrics and the share of solvable levels.  ``levels`` int32 [n, 80] or a
+    single [80] row; every env mode, tabular or not.  Not in the reference."""
+    single = levels.dim() == 1
+    lv = (levels.view(1, -1) if single else levels).contiguous()
+    if lv.dim() != 2 or lv.shape[1] != LEVEL_WORDS or lv.dtype != torch.int32:
+        raise ValueError(f"level_stats: levels must be int32 [n, {LEVEL_WORDS}] or [{LEVEL_WORDS}] "
+                         f"(got {lv.dtype} {tuple(levels.shape)})")
+    dist = torch.empty((lv.shape[0], spec.g2), dtype=torch.int32, device=lv.device) if return_dist else None
+    st = level_stats_raw(lv, spec, dist)
+    cols = [st[:, i] for i in range(LSTAT_OBJ_DIST)] + [st[:, LSTAT_OBJ_DIST:LSTAT_OBJ_DIST + spec.max_n_objs], dist]
+    if single:
+        cols = [None if c is None else c[0] for c in cols]
+    return LevelStats(*cols)
+
+
 class LevelEditor:
     """Device ACCEL editor (toued_level_edit; not in the reference): with probability ``p_edit`` a reset slot's
     generated level is replaced by ``num_edits`` small edits (``ops``: wall toggles, object moves, start moves,
-    per-type reward nudges of at most ``reward_delta``) of a parent level from the buffer."""
+    per-type reward nudges of at most ``reward_delta``) of a parent level from the buffer.
+
+    ``require_solvable``: a child without a positive reward reachable within its episode (toued_level_stats'
+    SOLVABLE == 0) is refused: the slot keeps the generator's level, all 80 words, and its flag comes back 0.  The
+    key schedule does not change, so each row is bit for bit the unfiltered child or the generator's row; a level
+    with random respawn (SOLVABLE == -1) passes.  ``last_rejected`` then holds the u8 [n] flags of the refused
+    rows of the last call (None without the filter)."""
 
     def __init__(self, spec: EnvSpec, ops="walls,objects,start", num_edits: int = 5, p_edit: float = 0.5,
-                 reward_delta: float = 0.1):
+                 reward_delta: float = 0.1, require_solvable: bool = False):
         self.spec = spec
         self.ops_mask = parse_edit_ops(ops)
         if num_edits < 0:
@@ -183,18 +243,29 @@ class LevelEditor:
         if not 0.0 <= p_edit <= 1.0:
             raise ValueError(f"edit_prob {p_edit} outside [0, 1]")
         self.num_edits, self.p_edit, self.reward_delta = int(num_edits), float(p_edit), float(reward_delta)
+        self.require_solvable = bool(require_solvable)
+        self.last_rejected = None
 
     def __call__(self, buffer_levels: torch.Tensor, parent_ids: torch.Tensor, keys: torch.Tensor,
                  levels: torch.Tensor) -> torch.Tensor:
         """Edits ``levels`` int32[n, 80] (the generator's levels of ``keys`` int32[n, 2]) in place: row j becomes the
-        edited ``buffer_levels[parent_ids[j]]`` where the row's own coin says so and ``parent_ids[j] >= 0``.  Returns
-        the u8 [n] flags of the rows that were replaced."""
+        edited ``buffer_levels[parent_ids[j]]`` where the row's own coin says so and ``parent_ids[j] >= 0`` (and,
+        with ``require_solvable``, the child is solvable).  Returns the u8 [n] flags of the rows that were
+        replaced."""
         n = keys.shape[0]
         edited = torch.empty((n,), dtype=torch.uint8, device=keys.device)
+        # the filter edits a copy, so that a refused row still holds the generator's level
+        target = levels.clone() if self.require_solvable else levels
         _lib.call("toued_level_edit", _lib.ptr(buffer_levels), _lib.ptr(parent_ids), _lib.ptr(keys.contiguous()), n,
                   self.spec.max_n_objs, self.spec.max_n_obj_types, self.p_edit, self.num_edits, self.ops_mask,
-                  self.reward_delta, _lib.ptr(levels), _lib.ptr(edited), _lib.stream_ptr())
-        return edited
+                  self.reward_delta, _lib.ptr(target), _lib.ptr(edited), _lib.stream_ptr())
+        if not self.require_solvable:
+            return edited
+        # the unedited rows of the copy are the generator's own, so the one select below serves them too
+        refused = level_stats_raw(target, self.spec)[:, LSTAT_SOLVABLE] == 0
+        self.last_rejected = (refused & (edited != 0)).to(torch.uint8)
+        levels.copy_(torch.where(refused[:, None], levels, target))
+        return edited * (1 - self.last_rejected)
 
 
 class GridWorld:

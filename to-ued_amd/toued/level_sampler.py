@@ -23,7 +23,9 @@ pi): no critic, no antagonist, no buffer state; every env mode, also with
 Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
-level instead of a fresh draw of the generator (toued.plr.reset_lowest_scoring).
+level instead of a fresh draw of the generator (toued.plr.reset_lowest_scoring); with ``--edit_require_solvable`` an
+edited level without a positive reward within reach (toued.env.level_stats) is refused and the slot keeps the
+generator's draw.
 Replay distribution (``--score_transform``, ``--staleness_coeff``): ``rank`` (the N best-scoring slots) and
 ``proportional`` (softmax of the score) are the reference's; ``rank_sampled`` (not in the reference) is Prioritized Level
 Replay's rank prioritisation, sampled: weight rank^(-1/score_temperature).  ``--staleness_coeff`` rho > 0 (not in the
@@ -131,7 +133,10 @@ class LevelSampler:
                                  f"{args.score_function}, which never resets a buffer slot)")
             self.editor = LevelEditor(self.spec, getattr(args, "edit_ops", "walls,objects,start"),
                                       getattr(args, "num_edits", 5), getattr(args, "edit_prob", 0.5),
-                                      getattr(args, "edit_reward_delta", 0.1))
+                                      getattr(args, "edit_reward_delta", 0.1),
+                                      require_solvable=bool(getattr(args, "edit_require_solvable", False)))
+        elif getattr(args, "edit_require_solvable", False):
+            raise ValueError("edit_require_solvable filters the level editor's children: it needs --level_editor accel")
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()

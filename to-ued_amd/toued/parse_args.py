@@ -28,6 +28,15 @@ Additions (all default to the reference's behaviour):
                         the level generator, ``accel`` with probability --edit_prob by --num_edits small edits
                         (--edit_ops: walls, objects, start, rewards; a reward moves by at most --edit_reward_delta) of a
                         high-scoring buffer level (ACCEL, Parker-Holder et al. 2022)
+  --edit_require_solvable  accel only: an edited level on which no positive-reward object can be reached from the start
+                        within max_steps_in_episode moves (toued.env.level_stats' ``solvable`` == 0) is refused and the
+                        slot keeps the generator's level; the key schedule is unchanged.  Refused without
+                        --level_editor accel
+  --level_metrics       add a ``levels`` dict to every log line: ACCEL's complexity metrics (Parker-Holder et al. 2022)
+                        of the levels the agents are on after the meta-step's sample -- ``solvable`` (share),
+                        ``n_walls``, ``reachable_frac``, ``ecc`` and ``nearest_reward_dist`` (means; NaN when no level
+                        has a reachable reward) -- and, with a level editor, the round's ``edited`` and
+                        ``edit_rejected`` counts.  One stats launch per meta-step; also with --use_es
   --score_transform rank_sampled  Prioritized Level Replay's rank prioritisation (Jiang et al. 2021): replay levels are
                         sampled without replacement with weight rank^(-1/score_temperature), rank 1 the highest score
                         (the reference's ``rank`` takes the N best-scoring slots, nothing is sampled)
@@ -137,6 +146,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="accel: comma list of the edit operations drawn from (walls, objects, start, rewards)")
     p.add_argument("--edit_reward_delta", type=float, default=0.1,
                    help="accel: the rewards op moves an object type's reward by uniform(-delta, delta)")
+    p.add_argument("--edit_require_solvable", action="store_true",
+                   help="accel: refuse an edited level without a positive reward reachable within its episode; the "
+                        "slot keeps the generator's level (needs --level_editor accel)")
+    p.add_argument("--level_metrics", action="store_true",
+                   help="Log the agents' levels' complexity metrics each meta-step (a 'levels' dict: share solvable, "
+                        "walls, reachable share, eccentricity, distance to the nearest reward; edit counts)")
     p.add_argument("--ref_quirk_checkpoint_init", action="store_true",
                    help="Checkpoint the initial LPG train state and level buffer, as the reference's _train_fn returns "
                         "them (train.py:52-57: the scan carry is never unpacked)")
@@ -152,4 +167,6 @@ def parse_args(cmd_args=None):
     if args.num_agents % args.num_mini_batches != 0:
         raise ValueError(f"Number of agents ({args.num_agents}) must be divisible by number of mini-batches "
                          f"({args.num_mini_batches})")
+    if args.edit_require_solvable and args.level_editor != "accel":
+        raise ValueError("--edit_require_solvable filters the level editor's children: it needs --level_editor accel")
     return args

@@ -101,7 +101,9 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: in
     this round's copy and never one of the slots being reset; ``sampler.last_edit`` keeps the parents and the flags.
     The generator still runs on the same keys and nothing else in the round changes.  Multi-GPU: both kernels read
     only replicated state (the buffer and the rng), so every rank computes identical children and no collective is
-    needed."""
+    needed.  With ``--edit_require_solvable`` a child without a reachable positive reward is refused and the slot keeps
+    the generator's level (LevelEditor(require_solvable=True): the stats kernel on the same stream and replicated
+    state, no host sync, no collective); ``sampler.last_edit["rejected"]`` marks those rows."""
     B = len(buffer)
     ids = torch.empty(n_new, dtype=torch.int32, device=buffer.score.device)
     _lib.call("toued_plr_reset_ids", B, n_new, _lib.ptr(buffer.score), _lib.ptr(buffer.active),
@@ -112,6 +114,8 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: in
     if editor is not None:
         parents = parent_ids(buffer, ids)
         sampler.last_edit = {"parent": parents, "edited": editor(buffer.levels, parents, keys, levels)}
+        if editor.require_solvable:     # --edit_require_solvable: the rows whose child the filter refused
+            sampler.last_edit["rejected"] = editor.last_rejected
     il = ids.long()
     buffer.levels.index_copy_(0, il, levels)
     buffer.score.index_fill_(0, il, 0.0)

@@ -94,7 +94,34 @@ class Trainer:
         self.rng, sub = ks[0, 0], ks[1, 0]
         self.buffer, self.agents = self.sampler.sample(sub, self.buffer, self.agents, self.sl)
         self.nans.raise_if_any()
+        if getattr(self.args, "level_metrics", False):
+            metrics = {**metrics, "levels": self.level_metrics()}
         return metrics
+
+    def level_metrics(self):
+        """--level_metrics: ACCEL's complexity metrics (Parker-Holder et al. 2022) of the levels the agents are on,
+        from one toued.env.level_stats launch, as 0-d device tensors: the share of solvable levels, the means of the
+        wall count, of the reachable share of the free cells and of the eccentricity, and the mean distance to the
+        nearest positive reward over the levels that have one (NaN when none has).  The ranks' shards are summed with
+        all_reduce_sum (sums and counts, so the means are over all agents).  With a level editor also the round's
+        ``edited`` and ``edit_rejected`` counts, which come from replicated state and are not reduced."""
+        from .env import level_stats
+        st = level_stats(self.agents.levels, self.sampler.spec)
+        f = lambda x: x.to(torch.float32)
+        has = st.nearest_pos >= 0
+        free = (st.cells - st.n_walls).clamp(min=1)
+        v = torch.stack([f(st.solvable == 1).sum(), f(st.n_walls).sum(), (f(st.n_reach) / f(free)).sum(),
+                         f(st.ecc).sum(), f(st.nearest_pos.clamp(min=0)).sum(), f(has).sum(),
+                         f(torch.ones_like(st.cells)).sum()])
+        self.world.all_reduce_sum(v)
+        out = {"solvable": v[0] / v[6], "n_walls": v[1] / v[6], "reachable_frac": v[2] / v[6], "ecc": v[3] / v[6],
+               "nearest_reward_dist": v[4] / v[5]}
+        if self.sampler.editor is not None:
+            le = self.sampler.last_edit or {}
+            zero = torch.zeros((), dtype=torch.int64, device=self.dev)
+            out["edited"] = le["edited"].sum() if "edited" in le else zero
+            out["edit_rejected"] = le["rejected"].sum() if "rejected" in le else zero
+        return out
 
     def finish(self):
         """End of training: report any device error a round left behind (synchronising once)."""
