@@ -154,6 +154,24 @@ int toued_level_edit(const int* buffer_levels, const int* parent_ids, const uint
 #define TOUED_LSTAT_OBJ_DIST 8
 int toued_level_stats(const int* levels, int n, int max_grid, int max_n_objs, int* stats, int* dist,
                       hipStream_t stream);
+/* Level distance (the duplicate check of DCD's level store and jaxued's PLR, and the diversity of a level buffer; not
+ * in the reference): for each of n query levels [n][80] the nearest of b corpus levels [b][80], both read only.
+ * The canonical record of a level is 54 words, what the env and the agent's lifetime read: max_steps, grid_size,
+ * start_pos, n_objs, random_respawn and lifetime (lifetime taken as 0 when include_lifetime == 0); obj_ids,
+ * static cell, reward, p_terminate and p_respawn of the object slots i < 8, every field of slot i taken as 0 when
+ * i >= clamp(n_objs, 0, 8), floats by bit pattern; and the 8 wall words keeping the bits of the cells c < g^2,
+ * g = clamp(grid_size, 0, 16).  buffer_id, word 7 and the per-type tables are not part of it.
+ *   d(a, b) = popcount(walls_a ^ walls_b) + the number of the 46 other canonical words that differ, in [0, 302];
+ * d == 0 exactly when the canonical records are equal.  Corpus entry j is eligible for query i when
+ * corpus_mask[j] != 0 (corpus_mask NULL: every j) and eligible == 0, or eligible == 1 and j != i, or eligible == 2
+ * and j < i.  Over the eligible j: nn_dist[i] the least d, nn_idx[i] the lowest j that attains it, dist_sum[i] the sum
+ * of d, count[i] their number; with none eligible INT_MAX, -1, 0 and 0.  The four outputs are int32 [n] and distinct.
+ * Integer work only, no host synchronisation, run-to-run bit-identical.  -1 for negative n, b outside [0, 65536]
+ * (dist_sum <= b * 302 stays an int32), eligible outside [0, 2], a NULL output with n > 0, NULL queries or corpus with
+ * n > 0 and b > 0; n == 0 and b == 0 succeed. */
+int toued_level_nearest(const int* queries, int n, const int* corpus, int b, const uint8_t* corpus_mask,
+                        int eligible, int include_lifetime, int* nn_dist, int* nn_idx, int* dist_sum, int* count,
+                        hipStream_t stream);
 
 /* ---- gymnax Environment plugin API (GridWorld, gridworld.py:72-211) ----
  * Worker i uses levels[i / W]; keys are per worker. */

@@ -43,6 +43,7 @@ _SIGS = {
     "toued_level_gen_masked": [_P, _P, _P, _P, _I, _P, _P],
     "toued_level_edit": [_P, _P, _P, _I, _I, _I, _F, _I, _I, _F, _P, _P, _P],
     "toued_level_stats": [_P, _I, _I, _I, _P, _P, _P],
+    "toued_level_nearest": [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
     "toued_gw_reset": [EnvSpecC, _P, _I, _P, _P, _P, _P, _I, _P],
     "toued_gw_step": [EnvSpecC, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "toued_batch_reset": [EnvSpecC, _P, _P, _I, _I, _P, _P, _P, _P],

@@ -223,6 +223,56 @@ def level_stats(levels: torch.Tensor, spec: EnvSpec, return_dist: bool = False) 
     return LevelStats(*cols)
 
 
+ELIGIBLE_MODES = ("all", "others", "lower")      # toued_level_nearest's eligible: 0, 1, 2
+LEVEL_DIST_MAX = 302                             # 46 words that differ + 256 wall bits
+
+
+class LevelNearest(NamedTuple):
+    """For each of n query levels, over the corpus entries eligible for it (toued_level_nearest), int32 [n] each (0-d
+    for a single query): ``dist`` the least level distance (2^31 - 1 when nothing is eligible), ``idx`` the lowest
+    corpus index that attains it (-1), ``dist_sum`` the sum of the distances and ``count`` the number of entries."""
+    dist: torch.Tensor
+    idx: torch.Tensor
+    dist_sum: torch.Tensor
+    count: torch.Tensor
+
+
+def level_nearest(queries: torch.Tensor, corpus: torch.Tensor, corpus_mask: torch.Tensor | None = None,
+                  eligible: str = "all", include_lifetime: bool = True) -> LevelNearest:
+    """The nearest of the ``corpus`` levels int32 [b, 80] (b <= 65536) to each of the ``queries`` int32 [n, 80] or
+    [80] (toued_level_nearest; one call on the current stream, no host synchronisation).  The distance is between the
+    levels' canonical records -- the 54 words the env and the agent's lifetime read: the six scalars, the five fields
+    of the object slots below n_objs and the wall bits of the cells inside the grid; not the buffer id or the per-type
+    tables -- the wall bits that differ plus the other words that differ (floats by bit pattern), an integer in
+    [0, 302] that is 0 exactly for equal records.  ``include_lifetime=False`` leaves the lifetime out.
+    ``corpus_mask`` (bool or uint8 [b]) keeps the entries where it is set; ``eligible``: "all", "others" (every entry
+    but the one with the query's own index) or "lower" (only the entries with a lower index than the query's).
+    Not in the reference."""
+    if eligible not in ELIGIBLE_MODES:
+        raise ValueError(f"level_nearest: eligible {eligible!r} not in {ELIGIBLE_MODES}")
+    single = queries.dim() == 1
+    q = (queries.view(1, -1) if single else queries).contiguous()
+    c = corpus.contiguous()
+    for name, x in (("queries", q), ("corpus", c)):
+        if x.dim() != 2 or x.shape[1] != LEVEL_WORDS or x.dtype != torch.int32:
+            raise ValueError(f"level_nearest: {name} must be int32 [n, {LEVEL_WORDS}]"
+                             f"{' or [' + str(LEVEL_WORDS) + ']' if name == 'queries' else ''} "
+                             f"(got {x.dtype} {tuple(x.shape)})")
+    n, b = q.shape[0], c.shape[0]
+    if c.device != q.device:
+        raise ValueError(f"level_nearest: queries on {q.device}, corpus on {c.device}")
+    if corpus_mask is not None:
+        if corpus_mask.shape != (b,) or corpus_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"level_nearest: corpus_mask must be bool or uint8 [{b}] "
+                             f"(got {corpus_mask.dtype} {tuple(corpus_mask.shape)})")
+        corpus_mask = corpus_mask.to(torch.uint8).contiguous()
+    out = torch.empty((4, n), dtype=torch.int32, device=q.device)
+    _lib.call("toued_level_nearest", _lib.ptr(q), n, _lib.ptr(c), b, _lib.ptr(corpus_mask),
+              ELIGIBLE_MODES.index(eligible), int(bool(include_lifetime)), _lib.ptr(out[0]), _lib.ptr(out[1]),
+              _lib.ptr(out[2]), _lib.ptr(out[3]), _lib.stream_ptr())
+    return LevelNearest(*((out[k, 0] if single else out[k]) for k in range(4)))
+
+
 class LevelEditor:
     """Device ACCEL editor (toued_level_edit; not in the reference): with probability ``p_edit`` a reset slot's
     generated level is replaced by ``num_edits`` small edits (``ops``: wall toggles, object moves, start moves,
@@ -232,40 +282,69 @@ class LevelEditor:
     SOLVABLE == 0) is refused: the slot keeps the generator's level, all 80 words, and its flag comes back 0.  The
     key schedule does not change, so each row is bit for bit the unfiltered child or the generator's row; a level
     with random respawn (SOLVABLE == -1) passes.  ``last_rejected`` then holds the u8 [n] flags of the refused
-    rows of the last call (None without the filter)."""
+    rows of the last call (None without the filter).
+
+    ``min_distance`` D > 0: a child whose level distance (``level_nearest``) to a buffer slot outside this round's
+    reset set, or to a lower-indexed row of this round's batch as edited, is below D is refused in the same way
+    (D = 1 refuses exact duplicates, which an edit that never applies produces).  The call then needs ``reset_ids``.
+    The batch is compared as it stands before any refusal, so a child can be refused because of an earlier child that
+    was itself refused: accepted, and deterministic.  The generator's own rows are never refused.
+    ``last_too_close`` holds the u8 [n] flags of the rows that were edited, passed the solvable filter and were too
+    close (None with D == 0); ``last_rejected`` keeps its meaning.  With D == 0 nothing is launched for it."""
 
     def __init__(self, spec: EnvSpec, ops="walls,objects,start", num_edits: int = 5, p_edit: float = 0.5,
-                 reward_delta: float = 0.1, require_solvable: bool = False):
+                 reward_delta: float = 0.1, require_solvable: bool = False, min_distance: int = 0):
         self.spec = spec
         self.ops_mask = parse_edit_ops(ops)
         if num_edits < 0:
             raise ValueError(f"num_edits {num_edits} is negative")
         if not 0.0 <= p_edit <= 1.0:
             raise ValueError(f"edit_prob {p_edit} outside [0, 1]")
+        if int(min_distance) != min_distance or min_distance < 0:
+            raise ValueError(f"edit_min_distance {min_distance} is not an integer >= 0")
         self.num_edits, self.p_edit, self.reward_delta = int(num_edits), float(p_edit), float(reward_delta)
         self.require_solvable = bool(require_solvable)
+        self.min_distance = int(min_distance)
         self.last_rejected = None
+        self.last_too_close = None
 
     def __call__(self, buffer_levels: torch.Tensor, parent_ids: torch.Tensor, keys: torch.Tensor,
-                 levels: torch.Tensor) -> torch.Tensor:
+                 levels: torch.Tensor, reset_ids: torch.Tensor | None = None) -> torch.Tensor:
         """Edits ``levels`` int32[n, 80] (the generator's levels of ``keys`` int32[n, 2]) in place: row j becomes the
-        edited ``buffer_levels[parent_ids[j]]`` where the row's own coin says so and ``parent_ids[j] >= 0`` (and,
-        with ``require_solvable``, the child is solvable).  Returns the u8 [n] flags of the rows that were
+        edited ``buffer_levels[parent_ids[j]]`` where the row's own coin says so and ``parent_ids[j] >= 0`` (and
+        the child passes the filters).  ``reset_ids`` int [n]: the buffer slots this round refills, which the
+        ``min_distance`` filter leaves out of its comparison.  Returns the u8 [n] flags of the rows that were
         replaced."""
         n = keys.shape[0]
         edited = torch.empty((n,), dtype=torch.uint8, device=keys.device)
-        # the filter edits a copy, so that a refused row still holds the generator's level
-        target = levels.clone() if self.require_solvable else levels
+        filtered = self.require_solvable or self.min_distance > 0
+        if self.min_distance > 0 and reset_ids is None:
+            raise ValueError("LevelEditor(min_distance > 0) needs reset_ids, the buffer slots of this round's rows")
+        # the filters edit a copy, so that a refused row still holds the generator's level
+        target = levels.clone() if filtered else levels
         _lib.call("toued_level_edit", _lib.ptr(buffer_levels), _lib.ptr(parent_ids), _lib.ptr(keys.contiguous()), n,
                   self.spec.max_n_objs, self.spec.max_n_obj_types, self.p_edit, self.num_edits, self.ops_mask,
                   self.reward_delta, _lib.ptr(target), _lib.ptr(edited), _lib.stream_ptr())
-        if not self.require_solvable:
+        if not filtered:
             return edited
-        # the unedited rows of the copy are the generator's own, so the one select below serves them too
-        refused = level_stats_raw(target, self.spec)[:, LSTAT_SOLVABLE] == 0
-        self.last_rejected = (refused & (edited != 0)).to(torch.uint8)
+        was_edited = edited != 0
+        refused = None
+        if self.require_solvable:
+            # the unedited rows of the copy are the generator's own, so the one select below serves them too
+            refused = level_stats_raw(target, self.spec)[:, LSTAT_SOLVABLE] == 0
+            self.last_rejected = (refused & was_edited).to(torch.uint8)
+        if self.min_distance > 0:
+            outside = torch.ones((buffer_levels.shape[0],), dtype=torch.uint8, device=keys.device)
+            outside.index_fill_(0, reset_ids.long(), 0)
+            near = torch.minimum(level_nearest(target, buffer_levels, outside).dist,
+                                 level_nearest(target, target, eligible="lower").dist)
+            close = (near < self.min_distance) & was_edited
+            if refused is not None:
+                close = close & ~refused
+            self.last_too_close = close.to(torch.uint8)
+            refused = close if refused is None else refused | close
         levels.copy_(torch.where(refused[:, None], levels, target))
-        return edited * (1 - self.last_rejected)
+        return edited * (~(refused & was_edited)).to(torch.uint8)
 
 
 class GridWorld:

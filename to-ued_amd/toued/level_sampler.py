@@ -25,7 +25,8 @@ with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
 level instead of a fresh draw of the generator (toued.plr.reset_lowest_scoring); with ``--edit_require_solvable`` an
 edited level without a positive reward within reach (toued.env.level_stats) is refused and the slot keeps the
-generator's draw.
+generator's draw, and so is, with ``--edit_min_distance D``, one closer than D (toued.env.level_nearest) to a level the
+buffer keeps or to an earlier child of the round: D = 1 refuses exact duplicates.
 Replay distribution (``--score_transform``, ``--staleness_coeff``): ``rank`` (the N best-scoring slots) and
 ``proportional`` (softmax of the score) are the reference's; ``rank_sampled`` (not in the reference) is Prioritized Level
 Replay's rank prioritisation, sampled: weight rank^(-1/score_temperature).  ``--staleness_coeff`` rho > 0 (not in the
@@ -134,9 +135,14 @@ class LevelSampler:
             self.editor = LevelEditor(self.spec, getattr(args, "edit_ops", "walls,objects,start"),
                                       getattr(args, "num_edits", 5), getattr(args, "edit_prob", 0.5),
                                       getattr(args, "edit_reward_delta", 0.1),
-                                      require_solvable=bool(getattr(args, "edit_require_solvable", False)))
+                                      require_solvable=bool(getattr(args, "edit_require_solvable", False)),
+                                      min_distance=getattr(args, "edit_min_distance", 0))
         elif getattr(args, "edit_require_solvable", False):
             raise ValueError("edit_require_solvable filters the level editor's children: it needs --level_editor accel")
+        elif getattr(args, "edit_min_distance", 0):
+            raise ValueError("edit_min_distance filters the level editor's children: it needs --level_editor accel")
+        if getattr(args, "buffer_diversity", False) and args.score_function == "random":
+            raise ValueError("buffer_diversity measures the level buffer: score_function random has none")
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()

@@ -32,6 +32,17 @@ Additions (all default to the reference's behaviour):
                         within max_steps_in_episode moves (toued.env.level_stats' ``solvable`` == 0) is refused and the
                         slot keeps the generator's level; the key schedule is unchanged.  Refused without
                         --level_editor accel
+  --edit_min_distance D  accel only: an edited level whose level distance (toued.env.level_nearest: wall bits that
+                        differ plus the other words of the level's canonical record that differ, 0 to 302) to a level
+                        the buffer keeps this round, or to an earlier child of the round, is below D is refused and the slot
+                        keeps the generator's level; the key schedule is unchanged.  1 refuses exact duplicates of the
+                        parent (every edit of a child can be a no-op); 0, the default, checks nothing.  Refused without
+                        --level_editor accel
+  --buffer_diversity    add a ``buffer`` dict to every log line, from one level_nearest launch of the level buffer
+                        against itself: ``unique_frac`` (the share of slots that are the first of their identity
+                        class), ``nn_dist`` (the mean distance to the nearest other slot), ``pair_dist`` (the mean
+                        distance over all pairs) and, with a level editor, ``edit_too_close`` (the round's count of
+                        children --edit_min_distance refused).  Refused with --score_function random (no buffer)
   --level_metrics       add a ``levels`` dict to every log line: ACCEL's complexity metrics (Parker-Holder et al. 2022)
                         of the levels the agents are on after the meta-step's sample -- ``solvable`` (share),
                         ``n_walls``, ``reachable_frac``, ``ecc`` and ``nearest_reward_dist`` (means; NaN when no level
@@ -149,6 +160,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--edit_require_solvable", action="store_true",
                    help="accel: refuse an edited level without a positive reward reachable within its episode; the "
                         "slot keeps the generator's level (needs --level_editor accel)")
+    p.add_argument("--edit_min_distance", type=int, default=0,
+                   help="accel: refuse an edited level closer than this level distance to a level the buffer keeps or "
+                        "to an earlier child of the round (1: exact duplicates; 0: no check; needs --level_editor "
+                        "accel)")
+    p.add_argument("--buffer_diversity", action="store_true",
+                   help="Log the level buffer's diversity each meta-step (a 'buffer' dict: share of unique levels, "
+                        "mean nearest-neighbour and pairwise level distance; not with --score_function random)")
     p.add_argument("--level_metrics", action="store_true",
                    help="Log the agents' levels' complexity metrics each meta-step (a 'levels' dict: share solvable, "
                         "walls, reachable share, eccentricity, distance to the nearest reward; edit counts)")
@@ -169,4 +187,10 @@ def parse_args(cmd_args=None):
                          f"({args.num_mini_batches})")
     if args.edit_require_solvable and args.level_editor != "accel":
         raise ValueError("--edit_require_solvable filters the level editor's children: it needs --level_editor accel")
+    if args.edit_min_distance < 0:
+        raise ValueError(f"--edit_min_distance {args.edit_min_distance} is negative")
+    if args.edit_min_distance and args.level_editor != "accel":
+        raise ValueError("--edit_min_distance filters the level editor's children: it needs --level_editor accel")
+    if args.buffer_diversity and args.score_function == "random":
+        raise ValueError("--buffer_diversity measures the level buffer: --score_function random has none")
     return args

@@ -103,7 +103,10 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: in
     only replicated state (the buffer and the rng), so every rank computes identical children and no collective is
     needed.  With ``--edit_require_solvable`` a child without a reachable positive reward is refused and the slot keeps
     the generator's level (LevelEditor(require_solvable=True): the stats kernel on the same stream and replicated
-    state, no host sync, no collective); ``sampler.last_edit["rejected"]`` marks those rows."""
+    state, no host sync, no collective); ``sampler.last_edit["rejected"]`` marks those rows.  With
+    ``--edit_min_distance D`` a child closer than D (toued.env.level_nearest) to a buffer slot outside ``ids`` or to an
+    earlier row of this round is refused in the same way (LevelEditor(min_distance=D): two more launches on the same
+    stream and replicated state); ``sampler.last_edit["too_close"]`` marks those rows."""
     B = len(buffer)
     ids = torch.empty(n_new, dtype=torch.int32, device=buffer.score.device)
     _lib.call("toued_plr_reset_ids", B, n_new, _lib.ptr(buffer.score), _lib.ptr(buffer.active),
@@ -113,9 +116,15 @@ def reset_lowest_scoring(sampler, rng: torch.Tensor, buffer, n_new: int, now: in
     editor = getattr(sampler, "editor", None)
     if editor is not None:
         parents = parent_ids(buffer, ids)
-        sampler.last_edit = {"parent": parents, "edited": editor(buffer.levels, parents, keys, levels)}
+        if editor.min_distance > 0:     # --edit_min_distance: the filter compares with the slots outside ids
+            flags = editor(buffer.levels, parents, keys, levels, reset_ids=ids)
+        else:
+            flags = editor(buffer.levels, parents, keys, levels)
+        sampler.last_edit = {"parent": parents, "edited": flags}
         if editor.require_solvable:     # --edit_require_solvable: the rows whose child the filter refused
             sampler.last_edit["rejected"] = editor.last_rejected
+        if editor.min_distance > 0:
+            sampler.last_edit["too_close"] = editor.last_too_close
     il = ids.long()
     buffer.levels.index_copy_(0, il, levels)
     buffer.score.index_fill_(0, il, 0.0)

@@ -96,7 +96,24 @@ class Trainer:
         self.nans.raise_if_any()
         if getattr(self.args, "level_metrics", False):
             metrics = {**metrics, "levels": self.level_metrics()}
+        if getattr(self.args, "buffer_diversity", False):
+            metrics = {**metrics, "buffer": self.buffer_diversity()}
         return metrics
+
+    def buffer_diversity(self):
+        """--buffer_diversity: how different the level buffer's levels are, from one toued.env.level_nearest launch of
+        the buffer against itself (every slot but the query's own), as 0-d device tensors: ``unique_frac``, the share
+        of slots that are the first of their identity class (no other slot at distance 0, or only higher ones);
+        ``nn_dist``, the mean distance to the nearest other slot; ``pair_dist``, the mean distance over all ordered
+        pairs.  The buffer is replicated, so nothing is reduced across ranks.  With a level editor also
+        ``edit_too_close``, the round's count of children that --edit_min_distance refused."""
+        from .level_stats import diversity_metrics
+        out = diversity_metrics(self.buffer.levels)
+        if self.sampler.editor is not None:
+            le = self.sampler.last_edit or {}
+            out["edit_too_close"] = (le["too_close"].sum() if "too_close" in le
+                                     else torch.zeros((), dtype=torch.int64, device=self.dev))
+        return out
 
     def level_metrics(self):
         """--level_metrics: ACCEL's complexity metrics (Parker-Holder et al. 2022) of the levels the agents are on,
