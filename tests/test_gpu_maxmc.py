@@ -24,9 +24,13 @@ NEG_INF = float("-inf")
 
 # (N, T, W, D, p_done).  The kernel walks time in chunks of 2048 // min(W, 256) steps: T = 1000 at W = 64 is 31 chunks
 # of 32 steps and one of 8; T = 33 at W = 96 is a chunk of 21 and one of 12; W = 200 leaves a worker tile that is no
-# multiple of 64; W = 300 is a tile of 256 workers and one of 44; D = 5409 is the largest critic row of any mode
+# multiple of 64; W = 300 is a tile of 256 workers and one of 44; D = 5409 is the largest critic row of any mode.
+# The seams of the loader shared with k_value_loss_scores (SEAMS is the same list in test_gpu_vscore.py): T one chunk
+# exactly (W = 256: 8 steps) and one step more, where the double buffer flips with a one-row chunk; a second tile of a
+# single worker; W = 1 with a chunk boundary at the last step
+SEAMS = [(2, 8, 256, 7, 0.3), (2, 9, 256, 7, 0.3), (1, 9, 257, 7, 0.3), (1, 2049, 1, 7, 0.2)]
 CASES = [(3, 1, 64, 10, 0.5), (5, 20, 1, 65, 0.2), (2, 33, 96, 65, 0.0), (2, 20, 64, 2, 1.0),
-         (2, 1000, 64, 3201, 0.05), (1, 300, 200, 5409, 0.1), (1, 40, 300, 65, 0.1), (0, 20, 64, 65, 0.1)]
+         (2, 1000, 64, 3201, 0.05), (1, 300, 200, 5409, 0.1), (1, 40, 300, 65, 0.1), (0, 20, 64, 65, 0.1)] + SEAMS
 
 
 @functools.lru_cache(maxsize=None)

@@ -24,12 +24,15 @@
 //     in chunks of 2048 pairs, pair e = chunk * 2048 + i * 512 + tid, 4 per thread.  All 8 loads of a chunk are issued,
 //     non-temporal, before the first use, and the next chunk's before the current chunk's arithmetic.  Nothing is
 //     sequential: no barrier between the staging barrier and the final reduction, and W > 512 needs nothing special.
-//   * Each thread adds its terms into three f64 partial sums (f32 -> f64 is exact) in the order of its pairs; the 512
-//     partials are reduced by a fixed tree in LDS, divided by (double)W * T (the entropy also by log 5) and rounded to
-//     f32 once: no atomics, the same bits on every run, and a function of agent a's rows only.
-#include "common.h"
+//   * Three f64 partial sums per thread, reduced and rounded once as trajscore_dev.h describes (the entropy is also
+//     divided by log 5).
+#include "trajscore_dev.h"
 
 namespace {
+
+using trajscore::block_reduce;
+using trajscore::clamp_row;
+using trajscore::trajscore_check;
 
 constexpr int kPsThreads = 512;
 constexpr int kPsPairs = 4;                          // (worker, step) pairs per thread and chunk
@@ -69,8 +72,7 @@ TOUED_DEV float plog_sum(float x) {
 // The three per-step terms of one (worker, step) pair from the table in LDS; `last` is row D-1.
 TOUED_DEV void policy_terms(const float* tab, const float* last, unsigned dmax, int idx, int tm, float& H, float& lc,
                             float& mm) {
-  // an index outside the table is held to its last row (no trajectory of toued_rollout has one)
-  const unsigned i = (unsigned)idx < dmax ? (unsigned)idx : dmax;
+  const unsigned i = clamp_row(idx, dmax);
   const float c = __fmul_rn((float)tm, 0.001f);
   float l[5];
 #pragma unroll
@@ -171,15 +173,7 @@ __global__ void __launch_bounds__(kPsThreads) k_policy_scores(
   red[tid] = sh;
   red[kPsThreads + tid] = sl;
   red[2 * kPsThreads + tid] = sm;
-  __syncthreads();
-  for (int s = kPsThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      red[tid] += red[tid + s];
-      red[kPsThreads + tid] += red[kPsThreads + tid + s];
-      red[2 * kPsThreads + tid] += red[2 * kPsThreads + tid + s];
-    }
-    __syncthreads();
-  }
+  block_reduce<kPsThreads, 3, false>(red, nullptr, tid);
   if (tid == 0) {
     const double cnt = (double)W * (double)T;
     if (entropy != nullptr) entropy[a] = (float)(red[0] / cnt / kPsLog5);
@@ -194,12 +188,8 @@ extern "C" {
 
 int toued_policy_scores(int N, int W, int T, int D, const float* theta, const int* tidx, const int* ttime,
                         float* entropy, float* least_conf, float* min_margin, float* steps, hipStream_t stream) {
-  TOUED_REQUIRE(N >= 0 && W >= 1 && T >= 1 && D >= 2, "toued_policy_scores: N=%d W=%d T=%d D=%d (need N >= 0, "
-                "W >= 1, T >= 1, D >= 2)", N, W, T, D);
-  TOUED_REQUIRE((long)W * T < (1L << 31), "toued_policy_scores: W=%d x T=%d steps per agent, limit 2^31", W, T);
-  TOUED_REQUIRE(D <= kPsMaxD, "toued_policy_scores: D=%d, an actor table of more than %d rows does not fit in LDS", D,
-                kPsMaxD);
-  if (N == 0) return 0;
+  const int go = trajscore_check("toued_policy_scores", N, W, T, D, kPsMaxD, "an actor table", "rows");
+  if (go <= 0) return go;
   TOUED_REQUIRE(theta && tidx && ttime, "toued_policy_scores: null input buffer");
   TOUED_REQUIRE(entropy || least_conf || min_margin, "toued_policy_scores: entropy, least_conf and min_margin are "
                 "all null");

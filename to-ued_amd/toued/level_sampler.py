@@ -40,6 +40,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -50,12 +51,45 @@ from .agents import (DENSE0_HASH, AgentBatch, AgentHyperparams, create_agents, c
 from .env import L_BUFID, L_LIFETIME, LevelEditor, LevelGenerator, get_env_spec
 from .rollout import RolloutWrapper
 
-SCORE_FUNCTIONS = ["random", "frozen", "alg_regret", "positive_value_loss", "l1_value_loss", "optimal_regret"]
-VALUE_LOSS_FUNCTIONS = ("positive_value_loss", "l1_value_loss")
-MOMENT_SCORE_FUNCTIONS = ("return_variance",)   # accepted beside SCORE_FUNCTIONS: toued.plr.MOMENT_FUNCTIONS
-RETURN_SCORE_FUNCTIONS = ("max_mc",)            # accepted beside SCORE_FUNCTIONS: toued.plr.RETURN_FUNCTIONS
-# accepted beside SCORE_FUNCTIONS: toued.plr.POLICY_FUNCTIONS
-POLICY_SCORE_FUNCTIONS = ("policy_entropy", "least_confidence", "min_margin")
+
+class ScoreFunction(NamedTuple):
+    """What a --score_function needs.  ``family`` groups the names (the views below, toued.plr's dicts).  A function
+    is called with (sampler, keys, levels, theta), then the agents' value critics if ``critic``, then the slots'
+    LevelBuffer.max_return if ``max_return`` (it then gives back (score, the new max_return))."""
+    family: str
+    scores: bool = True            # False: never called, no buffer slot is ever scored or reset
+    buffer: bool = True            # False: no level buffer at all
+    tabular: str | None = None     # why it needs a tabular mode: the end of the error's text
+    critic: bool = False           # reads AgentBatch.vcrit: refused with --use_es and when it is None
+    max_return: bool = False
+
+
+# every --score_function, in the order the error message lists them (the reference's, optimal_regret, the rest)
+SCORE_TABLE = {
+    "random": ScoreFunction("none", scores=False, buffer=False),
+    "frozen": ScoreFunction("none", scores=False),
+    "alg_regret": ScoreFunction("regret"),
+    "positive_value_loss": ScoreFunction("value_loss", critic=True),
+    "l1_value_loss": ScoreFunction("value_loss", critic=True),
+    "optimal_regret": ScoreFunction("regret", tabular="the optimal return is not defined for"),
+    "return_variance": ScoreFunction("moment", tabular="the agent is not a table over the states of"),
+    "max_mc": ScoreFunction("return", critic=True, max_return=True),
+    "policy_entropy": ScoreFunction("policy"),
+    "least_confidence": ScoreFunction("policy"),
+    "min_margin": ScoreFunction("policy"),
+}
+
+
+def score_family(*families: str) -> tuple:
+    return tuple(n for n, f in SCORE_TABLE.items() if f.family in families)
+
+
+# views of the table
+SCORE_FUNCTIONS = list(score_family("none", "regret", "value_loss"))
+VALUE_LOSS_FUNCTIONS = score_family("value_loss")
+MOMENT_SCORE_FUNCTIONS = score_family("moment")
+RETURN_SCORE_FUNCTIONS = score_family("return")
+POLICY_SCORE_FUNCTIONS = score_family("policy")
 SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
 TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
@@ -108,13 +142,12 @@ class LevelSampler:
         self.spec, self.max_rollout_len, self.max_lifetime = get_env_spec(self.env_mode)
         self.rollout_manager = RolloutWrapper(self.env_mode, args.train_rollout_len, self.max_rollout_len,
                                               args.env_workers)
-        if args.score_function == "optimal_regret" and not self.spec.tabular:
-            raise ValueError(f"Level score function optimal_regret needs a tabular environment mode: the optimal "
-                             f"return is not defined for {self.env_mode}")
-        if args.score_function in MOMENT_SCORE_FUNCTIONS and not self.spec.tabular:
-            raise ValueError(f"Level score function {args.score_function} needs a tabular environment mode: the "
-                             f"agent is not a table over the states of {self.env_mode}")
-        if args.score_function in VALUE_LOSS_FUNCTIONS + RETURN_SCORE_FUNCTIONS and args.use_es:
+        # an unknown name is refused below, after the checks that come before it: until then it needs nothing
+        needs = SCORE_TABLE.get(args.score_function, ScoreFunction("unknown"))
+        if needs.tabular and not self.spec.tabular:
+            raise ValueError(f"Level score function {args.score_function} needs a tabular environment mode: "
+                             f"{needs.tabular} {self.env_mode}")
+        if needs.critic and args.use_es:
             raise ValueError(f"Level score function {args.score_function} needs the agents' value critics, which "
                              f"--use_es does not train")
         self.regret_eval = getattr(args, "regret_eval", "sampled")
@@ -129,7 +162,7 @@ class LevelSampler:
             raise ValueError(f"level_editor {level_editor} not in {LEVEL_EDITORS}")
         self.editor = None
         if level_editor == "accel":
-            if args.score_function in ("random", "frozen"):
+            if not needs.scores:
                 raise ValueError(f"level_editor accel needs a score function with a reset round (got "
                                  f"{args.score_function}, which never resets a buffer slot)")
             self.editor = LevelEditor(self.spec, getattr(args, "edit_ops", "walls,objects,start"),
@@ -141,21 +174,20 @@ class LevelSampler:
             raise ValueError("edit_require_solvable filters the level editor's children: it needs --level_editor accel")
         elif getattr(args, "edit_min_distance", 0):
             raise ValueError("edit_min_distance filters the level editor's children: it needs --level_editor accel")
-        if getattr(args, "buffer_diversity", False) and args.score_function == "random":
+        if getattr(args, "buffer_diversity", False) and not needs.buffer:
             raise ValueError("buffer_diversity measures the level buffer: score_function random has none")
         self.last_edit = None
         self.agent_hypers = AgentHyperparams.from_args(args)
         self.agent_hypers.check_supported()
-        known = SCORE_FUNCTIONS + list(MOMENT_SCORE_FUNCTIONS + RETURN_SCORE_FUNCTIONS + POLICY_SCORE_FUNCTIONS)
-        if args.score_function not in known:
-            raise ValueError(f"Level score function {args.score_function} not in known functions: {known}")
+        if args.score_function not in SCORE_TABLE:
+            raise ValueError(f"Level score function {args.score_function} not in known functions: {list(SCORE_TABLE)}")
         if args.score_transform not in SCORE_TRANSFORMS:
             raise ValueError(
                 f"Level score transform {args.score_transform} not in known transforms: {SCORE_TRANSFORMS}")
         self.staleness_coeff = float(getattr(args, "staleness_coeff", 0.0))
         if not 0.0 <= self.staleness_coeff <= 1.0:
             raise ValueError(f"staleness_coeff {self.staleness_coeff} not in [0, 1]")
-        if self.staleness_coeff > 0.0 and args.score_function in ("random", "frozen"):
+        if self.staleness_coeff > 0.0 and not needs.scores:
             raise ValueError(f"staleness_coeff > 0 needs a score function that scores buffer slots (got "
                              f"{args.score_function}, which never scores one)")
         self.score_function = args.score_function
@@ -219,7 +251,7 @@ class LevelSampler:
         B = self.buffer_size
         stamp = torch.zeros(B, dtype=torch.int32, device=self.dev) if self.staleness_coeff > 0.0 else None
         max_return = (torch.full((B,), float("-inf"), dtype=torch.float32, device=self.dev)
-                      if self.score_function in RETURN_SCORE_FUNCTIONS else None)
+                      if SCORE_TABLE[self.score_function].max_return else None)
         return LevelBuffer(levels, torch.zeros(B, device=self.dev), torch.zeros(B, dtype=torch.bool, device=self.dev),
                            torch.ones(B, dtype=torch.bool, device=self.dev), stamp, max_return=max_return)
 

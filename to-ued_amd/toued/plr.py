@@ -68,7 +68,7 @@ from .a2c import A2CHyperparams, A2CTrainer
 from .debug import nan_checker
 from .agents import AgentBatch, create_agents, eval_agent, eval_agent_reset
 from .env import L_BUFID
-from .level_sampler import TRANSFORM_CODES
+from .level_sampler import SCORE_TABLE, TRANSFORM_CODES, score_family
 from .rollout import Transition
 
 
@@ -201,9 +201,6 @@ def optimal_regret(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta:
                                                                       sampler.env_workers)
 
 
-REGRET_FUNCTIONS = {"alg_regret": algorithmic_regret, "optimal_regret": optimal_regret}
-
-
 def return_variance(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor) -> torch.Tensor:
     """The exact variance of n LPG agents' first-episode returns on their tabular levels over the eval rollout length
     (RolloutWrapper.policy_return_moments): zero on a level the agent always or never solves, largest where the
@@ -214,10 +211,6 @@ def return_variance(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta
         return torch.zeros(0, device=levels.device)
     ro = sampler.rollout_manager
     return ro.policy_return_moments(levels, lpg_theta, ro.eval_rollout_len)[1]
-
-
-# the scores from the moments of the agent's own return: the regret functions' signature
-MOMENT_FUNCTIONS = {"return_variance": return_variance}
 
 
 # value_loss_scores keeps one chunk of agents' eval trajectories at a time (14 bytes per worker and step) under this
@@ -237,17 +230,21 @@ def value_loss_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_the
     The agents go through in chunks whose trajectories fit VALUE_LOSS_SCRATCH_BYTES (``chunk_agents`` overrides the
     chunk size); an agent's scores depend on its own key, level, actor and critic only, so the chunking changes
     no bit."""
-    n = keys.shape[0]
-    dev = keys.device
-    pvl = torch.empty(n, dtype=torch.float32, device=dev)
-    l1 = torch.empty(n, dtype=torch.float32, device=dev)
     ro = sampler.rollout_manager
-    vcrit = vcrit.reshape(n, ro.obs_dim)
+    vcrit = vcrit.reshape(keys.shape[0], ro.obs_dim)
+    return _chunked_scores(sampler, keys, levels, lpg_theta, chunk_agents, 2, lambda lo, hi, out: ro.value_loss_scores(
+        out, vcrit[lo:hi].contiguous(), sampler.args.gamma, sampler.args.gae_lambda))
+
+
+def _chunked_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
+                    chunk_agents: int | None, k: int, per_chunk) -> tuple:
+    """``k`` scores f32 [n] of the n agents' eval trajectories, filled a chunk of agents at a time:
+    ``per_chunk(lo, hi, Transition of agents lo..hi-1)`` gives the k scores of those agents."""
+    outs = tuple(torch.empty(keys.shape[0], dtype=torch.float32, device=keys.device) for _ in range(k))
     for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
-        p, l = ro.value_loss_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, sampler.args.gae_lambda)
-        pvl[lo:hi] = p
-        l1[lo:hi] = l
-    return pvl, l1
+        for o, part in zip(outs, per_chunk(lo, hi, out)):
+            o[lo:hi] = part
+    return outs
 
 
 def _eval_trajectory_chunks(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
@@ -287,10 +284,6 @@ def l1_value_loss(sampler, keys, levels, lpg_theta, vcrit) -> torch.Tensor:
     return value_loss_scores(sampler, keys, levels, lpg_theta, vcrit)[1]
 
 
-# the scores that read the agents' value critics: the regret functions' arguments plus AgentBatch.vcrit's rows
-VALUE_LOSS_FUNCTIONS = {"positive_value_loss": positive_value_loss, "l1_value_loss": l1_value_loss}
-
-
 def max_mc_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor, vcrit: torch.Tensor,
                   prior: torch.Tensor, chunk_agents: int | None = None):
     """The MaxMC PLR score of n LPG agents (the maximum Monte Carlo regret estimate of Jiang et al. 2021,
@@ -303,22 +296,10 @@ def max_mc_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: 
     tabular level: any env mode.  The keys, the eval trajectory and the chunking are ``value_loss_scores``', so the
     scored trajectory is the one the other scores use, and the chunking changes no bit.  An extension: the reference's
     LevelSampler has no such score."""
-    n = keys.shape[0]
-    dev = keys.device
-    score = torch.empty(n, dtype=torch.float32, device=dev)
-    rmax = torch.empty(n, dtype=torch.float32, device=dev)
     ro = sampler.rollout_manager
-    vcrit = vcrit.reshape(n, ro.obs_dim)
-    for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
-        s, r = ro.max_mc_scores(out, vcrit[lo:hi].contiguous(), sampler.args.gamma, prior[lo:hi].contiguous())
-        score[lo:hi] = s
-        rmax[lo:hi] = r
-    return score, rmax
-
-
-# the scores from the returns of the agent's eval trajectory, remembered per buffer slot: the value-loss functions'
-# arguments plus the slots' LevelBuffer.max_return; they return (score, the slots' new max_return)
-RETURN_FUNCTIONS = {"max_mc": max_mc_scores}
+    vcrit = vcrit.reshape(keys.shape[0], ro.obs_dim)
+    return _chunked_scores(sampler, keys, levels, lpg_theta, chunk_agents, 2, lambda lo, hi, out: ro.max_mc_scores(
+        out, vcrit[lo:hi].contiguous(), sampler.args.gamma, prior[lo:hi].contiguous()))
 
 
 def policy_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: torch.Tensor,
@@ -331,15 +312,9 @@ def policy_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: 
     and no buffer state.  The keys, the eval trajectory and the chunking are ``value_loss_scores``', so the scored
     trajectory is the one the other scores use, and the chunking changes no bit.  An extension: the reference's
     LevelSampler has no such score."""
-    n = keys.shape[0]
-    dev = keys.device
-    ent = torch.empty(n, dtype=torch.float32, device=dev)
-    lc = torch.empty(n, dtype=torch.float32, device=dev)
-    mm = torch.empty(n, dtype=torch.float32, device=dev)
     ro = sampler.rollout_manager
-    for lo, hi, out in _eval_trajectory_chunks(sampler, keys, levels, lpg_theta, chunk_agents):
-        ent[lo:hi], lc[lo:hi], mm[lo:hi] = ro.policy_scores(out, lpg_theta[lo:hi].contiguous())
-    return ent, lc, mm
+    return _chunked_scores(sampler, keys, levels, lpg_theta, chunk_agents, 3,
+                           lambda lo, hi, out: ro.policy_scores(out, lpg_theta[lo:hi].contiguous()))
 
 
 def policy_entropy(sampler, keys, levels, lpg_theta) -> torch.Tensor:
@@ -354,8 +329,13 @@ def min_margin(sampler, keys, levels, lpg_theta) -> torch.Tensor:
     return policy_scores(sampler, keys, levels, lpg_theta)[2]
 
 
-# the scores that read nothing but the agent's own policy on its eval trajectory: the regret functions' signature
-POLICY_FUNCTIONS = {"policy_entropy": policy_entropy, "least_confidence": least_confidence, "min_margin": min_margin}
+# every score function that is called (level_sampler.SCORE_TABLE says with what), and its views by family
+SCORE_CALLS = {"alg_regret": algorithmic_regret, "positive_value_loss": positive_value_loss,
+               "l1_value_loss": l1_value_loss, "optimal_regret": optimal_regret, "return_variance": return_variance,
+               "max_mc": max_mc_scores, "policy_entropy": policy_entropy, "least_confidence": least_confidence,
+               "min_margin": min_margin}
+REGRET_FUNCTIONS, MOMENT_FUNCTIONS, VALUE_LOSS_FUNCTIONS, RETURN_FUNCTIONS, POLICY_FUNCTIONS = (
+    {n: SCORE_CALLS[n] for n in score_family(f)} for f in ("regret", "moment", "value_loss", "return", "policy"))
 
 
 # the regret round's eval draws ([eval_len][2n * W][4] u32, plus as much key-chain scratch) are made ahead when they fit
@@ -407,9 +387,8 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     """Returns (rng, buffer, new_levels [n_local, 64]) — new_levels for terminated agents, the
     caller keeps the old level elsewhere (``term_mask_fn``)."""
     world = sampler.world
-    return_fn = RETURN_FUNCTIONS.get(sampler.score_function)
-    value_loss = VALUE_LOSS_FUNCTIONS.get(sampler.score_function)
-    if (value_loss is not None or return_fn is not None) and agents.vcrit is None:
+    needs, score_fn = SCORE_TABLE[sampler.score_function], SCORE_CALLS[sampler.score_function]
+    if needs.critic and agents.vcrit is None:
         raise ValueError(f"Level score function {sampler.score_function} needs the agents' value critics "
                          f"(AgentBatch.vcrit is None)")
     N = agents.n if sl is None else sl[2]
@@ -423,7 +402,7 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     if side is None:
         side = sampler._plr_side = torch.cuda.Stream(device=dev)
     prior = rmax = None
-    if return_fn is not None:
+    if needs.max_return:
         if buffer.max_return is None:
             raise ValueError(f"Level score function {sampler.score_function} needs a level buffer with max_return "
                              f"(LevelSampler.initialize_buffer makes it; a checkpoint written without it has none)")
@@ -444,19 +423,15 @@ def plr_sample(sampler, rng: torch.Tensor, buffer, agents: AgentBatch, term: tor
     if sl is not None:
         keys = keys[sl[0]:sl[1]].contiguous()
     score = torch.zeros(agents.n, dtype=torch.float32, device=dev)
-    if value_loss is not None:
-        vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
-        regret = lambda s, k, lv, th, sel=slice(None): value_loss(s, k, lv, th, vcrit[sel].contiguous())
-    elif return_fn is not None:
-        vcrit = agents.vcrit.reshape(agents.n, sampler.obs_dim)
+    # what the function takes per agent beside the regret functions' arguments (SCORE_TABLE)
+    per_agent = ([agents.vcrit.reshape(agents.n, sampler.obs_dim)] if needs.critic else []) \
+        + ([prior] if needs.max_return else [])
 
-        def regret(s, k, lv, th, sel=slice(None)):
-            sc, rmax[sel] = return_fn(s, k, lv, th, vcrit[sel].contiguous(), prior[sel].contiguous())
-            return sc
-    else:
-        score_fn = (REGRET_FUNCTIONS.get(sampler.score_function) or POLICY_FUNCTIONS.get(sampler.score_function)
-                    or MOMENT_FUNCTIONS[sampler.score_function])
-        regret = lambda s, k, lv, th, sel=None: score_fn(s, k, lv, th)
+    def regret(s, k, lv, th, sel=slice(None)):
+        sc = score_fn(s, k, lv, th, *(x[sel].contiguous() for x in per_agent))
+        if needs.max_return:
+            sc, rmax[sel] = sc
+        return sc
     if sampler.regret_all_agents:
         score = regret(sampler, keys, agents.levels, agents.theta)
     else:

@@ -37,6 +37,21 @@ class Transition:
     done: torch.Tensor
 
 
+def _check_transition(name: str, transition: Transition):
+    """(N, T, W) of a trajectory that the score kernels read, its shapes checked against one another."""
+    N, T, W = transition.reward.shape
+    if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
+            or transition.done.shape != (N, T, W):
+        raise ValueError(f"{name}: obs_idx {tuple(transition.obs_idx.shape)}, reward "
+                         f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
+    return N, T, W
+
+
+def _critic_rows(vcrit: torch.Tensor, N: int) -> torch.Tensor:
+    """The value critics as contiguous rows [N, D], from [N, D] or the critic table [N, D, 1]."""
+    return vcrit.reshape(N, vcrit.shape[1]).contiguous()
+
+
 def split_rollouts() -> bool:
     """Train rollouts as draws + env chain (toued_rollout_draws / toued_rollout_env) unless TOUED_ROLLOUT_FUSED=1
     (the single-kernel toued_rollout; bit-identical)."""
@@ -260,12 +275,8 @@ class RolloutWrapper:
         (positive value loss, L1 value loss), f32 [N] each, the means over workers and steps of max(GAE, 0) and |GAE|
         with the value of meta/train.py:61-100 and the scan of util/metrics.py:17-38.  ``return_adv``: also the
         advantages f32 [N, T, W], bit-identical to toued.metrics.gae on the gathered values."""
-        N, T, W = transition.reward.shape
-        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
-                or transition.done.shape != (N, T, W):
-            raise ValueError(f"value_loss_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
-                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
-        vcrit = vcrit.reshape(N, vcrit.shape[1]).contiguous()     # [N, D] or the critic table [N, D, 1]
+        N, T, W = _check_transition("value_loss_scores", transition)
+        vcrit = _critic_rows(vcrit, N)
         dev = transition.reward.device
         pvl = torch.empty(N, dtype=torch.float32, device=dev)
         l1 = torch.empty(N, dtype=torch.float32, device=dev)
@@ -287,12 +298,8 @@ class RolloutWrapper:
         Environment Design").  Returns are discounted with ``gamma`` so that they live on the value critic's scale;
         the episode still open at the trajectory's end counts with its truncated return.  ``return_worker_max``: also
         each worker's best return, f32 [N, W]."""
-        N, T, W = transition.reward.shape
-        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
-                or transition.done.shape != (N, T, W):
-            raise ValueError(f"max_mc_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
-                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
-        vcrit = vcrit.reshape(N, vcrit.shape[1]).contiguous()     # [N, D] or the critic table [N, D, 1]
+        N, T, W = _check_transition("max_mc_scores", transition)
+        vcrit = _critic_rows(vcrit, N)
         dev = transition.reward.device
         if rmax_in is not None:
             if rmax_in.shape != (N,) or rmax_in.dtype != torch.float32 or rmax_in.device != dev:
@@ -315,11 +322,7 @@ class RolloutWrapper:
         pi) (Prioritized Level Replay, Jiang et al. 2021, Table 1).  Only the observations are read: no reward, no
         done flag, no value critic.  ``return_steps``: also the per-step terms f32 [N, 3, T, W] (entropy before the
         division by log 5, least confidence, min margin)."""
-        N, T, W = transition.reward.shape
-        if transition.obs_idx.shape != (N, T + 1, W) or transition.obs_time.shape != (N, T + 1, W) \
-                or transition.done.shape != (N, T, W):
-            raise ValueError(f"policy_scores: obs_idx {tuple(transition.obs_idx.shape)}, reward "
-                             f"{tuple(transition.reward.shape)}, done {tuple(transition.done.shape)}")
+        N, T, W = _check_transition("policy_scores", transition)
         dev = transition.reward.device
         if theta.dim() != 3 or theta.shape[0] != N or theta.shape[2] != 5 or theta.dtype != torch.float32 \
                 or theta.device != dev:

@@ -19,21 +19,11 @@ step is started).
     a device synchronise, after one warm-up round), the two alternated in one process.
 
 Prints one JSON line and writes it to --out."""
-import argparse
-import json
-import statistics
-import subprocess
 import sys
-import time
-from pathlib import Path
 
-ROOT = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "to-ued_amd"))
+import bench_trajscore as bt
 
-HBM_SPEC_TBS = 8.0          # MI355X HBM3E peak, datasheet
-HBM_COPY_TBS = 6.29         # what a float4 copy reaches
 BYTES_PER_PAIR = 13
-STEP_TIMEOUT_S = {"kernel": 240, "rounds": 300}
 
 
 def composed_max_mc(vcrit, idx, tm, rew, done, gamma):
@@ -61,134 +51,38 @@ def composed_max_mc(vcrit, idx, tm, rew, done, gamma):
 
 
 def step_kernel(reps: int) -> dict:
-    import numpy as np
-    import torch
     from toued import _lib
-    from toued.rollout import RolloutWrapper
-    gamma, lam = 0.99, 0.95
-    gl = float(np.float32(gamma * lam))
-    N, W = 512, 64
+    N, W = bt.N_AGENTS, bt.N_WORKERS
     out = []
-    for mode, T in (("all", 750), ("tabular", 2000)):
-        D = RolloutWrapper(mode, 20).obs_dim
-        g = torch.Generator(device="cuda").manual_seed(T)
-        vcrit = torch.randn((N, D), device="cuda", generator=g)
-        idx = torch.randint(0, D - 1, (N, T + 1, W), device="cuda", generator=g, dtype=torch.int32)
-        tm = torch.randint(0, 2000, (N, T + 1, W), device="cuda", generator=g, dtype=torch.int32)
-        rew = torch.randn((N, T, W), device="cuda", generator=g)
-        done = (torch.rand((N, T, W), device="cuda", generator=g) < 0.05).to(torch.uint8)
-        score, rmax = torch.empty(N, device="cuda"), torch.empty(N, device="cuda")
-        pvl, l1 = torch.empty(N, device="cuda"), torch.empty(N, device="cuda")
+    for mode, T in bt.SHAPES:
+        tr = bt.random_trajectory(mode, T)
+        D, gamma = tr["D"], 0.99
+        score, rmax = (tr["rew"].new_empty(N) for _ in range(2))
 
         def maxmc():
-            _lib.call("toued_max_mc_scores", N, W, T, D, _lib.ptr(vcrit), _lib.ptr(idx), _lib.ptr(tm), _lib.ptr(rew),
-                      _lib.ptr(done), gamma, None, _lib.ptr(score), _lib.ptr(rmax), None, _lib.stream_ptr())
+            _lib.call("toued_max_mc_scores", N, W, T, D, _lib.ptr(tr["vcrit"]), _lib.ptr(tr["idx"]), _lib.ptr(tr["tm"]),
+                      _lib.ptr(tr["rew"]), _lib.ptr(tr["done"]), gamma, None, _lib.ptr(score), _lib.ptr(rmax), None,
+                      _lib.stream_ptr())
             return score, rmax
 
-        def vscore():
-            _lib.call("toued_value_loss_scores", N, W, T, D, _lib.ptr(vcrit), _lib.ptr(idx), _lib.ptr(tm),
-                      _lib.ptr(rew), _lib.ptr(done), gamma, gl, _lib.ptr(pvl), _lib.ptr(l1), None, _lib.stream_ptr())
-
         def composed():
-            return composed_max_mc(vcrit, idx, tm, rew, done, gamma)
+            return composed_max_mc(tr["vcrit"], tr["idx"], tr["tm"], tr["rew"], tr["done"], gamma)
 
-        for _ in range(3):                                   # warm-up: code objects, allocator pools
-            k_out = [x.clone() for x in maxmc()]
-            vscore()
-            c_out = composed()
-        torch.cuda.synchronize()
         # the two paths agree (the kernel's chains are float32, the composed returns float64)
-        for a, b in zip(k_out, c_out):
-            assert torch.allclose(a, b, rtol=1e-4, atol=1e-4), (a[:4], b[:4])
-        fns = (("maxmc", maxmc), ("vscore", vscore), ("composed", composed))
-        times = {name: [] for name, _ in fns}
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(reps):
-            for name, fn in fns:
-                ev0.record()
-                fn()
-                ev1.record()
-                torch.cuda.synchronize()
-                times[name].append(ev0.elapsed_time(ev1))
-        med = {name: statistics.median(v) for name, v in times.items()}
+        times = bt.time_alternated((("maxmc", maxmc), ("vscore", bt.vscore_call(tr, T)), ("composed", composed)), reps,
+                                   dict(rtol=1e-4, atol=1e-4))
+        row, med = bt.timing_row(mode, T, D, reps, times)
         nbytes = BYTES_PER_PAIR * N * T * W
         tbs = nbytes / (med["maxmc"] * 1e-3) / 1e12
-        row = {"mode": mode, "N": N, "W": W, "T": T, "D": D, "reps": reps}
-        for name, v in times.items():
-            row.update({f"{name}_ms_median": round(med[name], 4), f"{name}_ms_min": round(min(v), 4),
-                        f"{name}_ms_max": round(max(v), 4)})
         row.update({"maxmc_over_vscore": round(med["maxmc"] / med["vscore"], 3),
                     "composed_over_maxmc": round(med["composed"] / med["maxmc"], 2),
                     "algorithmic_bytes": nbytes, "maxmc_TB_per_s": round(tbs, 3),
-                    "vscore_TB_per_s": round(nbytes / (med["vscore"] * 1e-3) / 1e12, 3),
-                    "fraction_of_hbm_spec_8.0": round(tbs / HBM_SPEC_TBS, 3),
-                    "fraction_of_hbm_copy_6.29": round(tbs / HBM_COPY_TBS, 3),
+                    "vscore_TB_per_s": round(nbytes / (med["vscore"] * 1e-3) / 1e12, 3), **bt.hbm_fractions(tbs),
                     "gate_maxmc_not_slower_than_composed": bool(med["maxmc"] <= med["composed"])})
         out.append(row)
     return {"kernel": out}
 
 
-def step_rounds(rounds: int) -> dict:
-    import torch
-    from toued.env import L_LIFETIME
-    from toued.parse_args import parse_args
-    from toued.train import Trainer
-    trs = {}
-    for sf in ("max_mc", "positive_value_loss"):
-        args = parse_args(["--env_mode", "all_shortlife", "--num_agents", "512", "--num_mini_batches", "1",
-                           "--score_function", sf])
-        trs[sf] = Trainer(args)
-
-    def one_round(tr):
-        tr.agents.step = tr.agents.levels[:, L_LIFETIME].clone()     # every agent terminated: all are scored
-        tr.buffer, tr.agents = tr.sampler.sample(tr.rng, tr.buffer, tr.agents)
-
-    times = {sf: [] for sf in trs}
-    for sf, tr in trs.items():
-        one_round(tr)                                                  # warm-up
-    for _ in range(3):                                                 # alternated
-        for sf, tr in trs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(rounds):
-                one_round(tr)
-            torch.cuda.synchronize()
-            times[sf].append((time.perf_counter() - t0) / rounds * 1e3)
-    return {"c3_regret_round": {sf: {"regret_round_ms": [round(x, 3) for x in v],
-                                     "regret_round_ms_median": round(statistics.median(v), 3)}
-                                for sf, v in times.items()}}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", type=str, default=str(ROOT / "profiles" / "maxmc" / "bench_maxmc.json"))
-    ap.add_argument("--step", choices=sorted(STEP_TIMEOUT_S), default=None, help="run one step in this process")
-    a = ap.parse_args()
-    if a.step is not None:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("bench_maxmc: needs the GPU (no CPU fallback)")
-        res = step_kernel(a.reps) if a.step == "kernel" else step_rounds(a.rounds)
-        print("BENCH_MAXMC_STEP " + json.dumps(res), flush=True)
-        return 0
-    out = {}
-    for step in ("kernel", "rounds"):
-        cmd = ["timeout", "-k", "10", str(STEP_TIMEOUT_S[step]), sys.executable, str(Path(__file__).resolve()),
-               "--step", step, "--reps", str(a.reps), "--rounds", str(a.rounds)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("BENCH_MAXMC_STEP ")]
-        if r.returncode != 0 or not lines:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            raise SystemExit(f"bench_maxmc: step {step} failed (exit status {r.returncode}); nothing more is run")
-        out.update(json.loads(lines[-1][len("BENCH_MAXMC_STEP "):]))
-    line = json.dumps(out)
-    print(line, flush=True)
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(line + "\n")
-    return 0 if all(k["gate_maxmc_not_slower_than_composed"] for k in out["kernel"]) else 1
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(bt.main("maxmc", __file__, step_kernel, ("max_mc", "positive_value_loss"),
+                     "gate_maxmc_not_slower_than_composed", {"kernel": 240, "rounds": 300}))
