@@ -257,6 +257,33 @@ int toued_policy_return(const int* levels, const float* theta, int n, int D, int
 int toued_policy_return_moments(const int* levels, const float* theta, int n, int D, int max_grid, int n_max,
                                 int tabular, int max_rollout_len, float* v0, float* var0, float* v_all,
                                 float* var_all, hipStream_t stream);
+/* The exact state occupancy of n tabular agents' own policies on their levels (RolloutWrapper.policy_occupancy), the
+ * forward counterpart of toued_policy_return: d_0 = 1 at (start cell, all used objects present) and, for
+ * t = 0 .. H-1 with H = min(max_steps_in_episode, max_rollout_len), every state s = (pos, e) sends
+ * d_t(s) pi_t(a|s) keep(col) pw[absent][R] to (next cell, (e \ col) | R) for every action a and every subset R of the
+ * absent objects, so d_t(s) = P(the first episode is still running at step t and is in state s).  pi_t is
+ * toued_policy_return's policy (f32 logits, f64 softmax); keep(col) = clamp(1 - sum of the collected objects'
+ * p_terminate, 0, 1), the env's own behaviour, where toued_policy_return follows the reference's DP and does not
+ * clamp.  Arguments as toued_policy_return's.  summary [n][8] (required):
+ *   0 ret              sum d pi r: V^pi_0(start), toued_policy_return's v0 from the other side
+ *   1 length           sum_t sum_s d_t(s), the expected number of steps of the first episode
+ *   2 p_early_term     sum d pi (1 - keep)
+ *   3 alive_end        sum_s d_H(s)
+ *   4 entropy          mean over the visited steps of H(pi_t(.|s)) / log 5
+ *   5 least_confidence mean over the visited steps of 1 - max pi
+ *   6 min_margin       mean over the visited steps of 1 - (max pi - second-largest pi)
+ *   7 ret_abs          sum d pi |r|, the error scale of column 0
+ * (4-6 are the d-weighted sums over length, 0 when length is 0).  visits (nullable) [n][S] = sum_t d_t(s), 0 at the
+ * invalid states; collected (nullable) [n][n_max] = the expected number of collections of each object; occ_all
+ * (nullable) [n][max_rollout_len][S] = d_t, rows t >= H zero.  With H = 0 everything is 0.  Mass is held as 64-bit
+ * fixed point (2^-62) and added with integer LDS atomics, the sums are f64 combined by a fixed tree: one launch,
+ * run-to-run bit-identical, level i's result depends on levels[i] and theta[i] only; every output is within
+ * 2^-23 * max(1, its value) of the f64 recursion (column 0: of ret_abs).  Errors (-1) as toued_policy_return's, and
+ * for a null summary or a table with more than six states per thread (no mode has one); n == 0 and
+ * max_rollout_len == 0 succeed. */
+int toued_policy_occupancy(const int* levels, const float* theta, int n, int D, int max_grid, int n_max,
+                           int tabular, int max_rollout_len, float* summary, float* visits, float* collected,
+                           float* occ_all, hipStream_t stream);
 
 
 /* ---- Level sampler (environments/level_sampler.py) ---- */

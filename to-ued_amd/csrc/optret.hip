@@ -37,6 +37,12 @@
 //   softmax_backup   sum_a pi(a) q(s, a) (and the variance beside it)         k_policy_return, k_policy_moments
 //   policy_items     a thread's items and their theta rows in registers       k_policy_return, k_policy_moments
 // k_optimal_return's backup, the max over the actions, is written in the kernel.
+//
+// k_policy_occupancy is the forward counterpart of k_policy_return: the state occupancy d_t(s) of the policy, pushed
+// from the start state through the same next-state, reward, keep and respawn tables (optret_setup, work_item,
+// policy_items), with the two value tables read as u64 fixed-point mass.  It holds 1 - p_term to [0, 1], as the env's
+// bernoulli(p_term) does; k_policy_return and k_policy_moments follow the reference's DP and do not clamp, so the
+// return obtained from the occupancy equals theirs on the levels whose collected sets have sum p_terminate <= 1.
 #include <type_traits>
 
 #include "env_dev.h"
@@ -482,6 +488,207 @@ __global__ __launch_bounds__(1024) void k_policy_moments(const int* __restrict__
   write_start<true>(T, ua, nxo, v0, var0);
 }
 
+// Occupancy mass is held in fixed point, scaled by 2^62, in the setup's two tables read as u64: a state's mass at
+// most 1 is at most 2^62, and a whole table sums to at most 2^62, far inside 64 bits.
+constexpr double kOccOne = 4611686018427387904.0;           // 2^62
+constexpr double kOccInv = 1.0 / 4611686018427387904.0;     // 2^-62, exact
+// the eight summary columns as the block's sums (4-6 before their division by the length): a thread adds to ret,
+// ret_abs and the three policy terms inside the time loop; its length (the sum of its items' visits) and alive_end are
+// filled after it, and p_early_term is a block-wide fixed-point sum beside the collections
+enum { OCC_RET = 0, OCC_LEN, OCC_PTERM, OCC_ALIVE, OCC_ENT, OCC_LC, OCC_MM, OCC_RABS, OCC_SUMS };
+// The expected collections of an object are a block-wide fixed-point sum too, scaled by 2^48 (a step adds at most 1
+// per object, so H < 2^15 steps fit 63 bits): collecting moves are rare, at most 5 * 2^(n_objs - 1) (state, action)
+// pairs per object and step, so the sum is within H * 5 * 2^(n_objs - 1) * 2^-48 of the f64 one (2^-30 at the
+// largest mode) and a thread keeps no register per object.
+constexpr double kColOne = 281474976710656.0;               // 2^48
+constexpr double kColInv = 1.0 / 281474976710656.0;
+
+// One state's forward step: the mass m = d_t(pos, e) > 0 goes, for every action a and every subset R of the absent
+// objects that respawns, as m pi(a) keep(col) pw[absent][R] into table `nxo` at (next cell, (e \ col) | R), truncated
+// to a multiple of 2^-62 and added with a 64-bit integer LDS atomic: integer sums are exact in any order, so the
+// tables do not depend on the order the waves run in.  The softmax is softmax_backup's (f64, from the f32 logits l);
+// the entropy is log(sum x) - sum x_a d_a / sum x with d_a = l_a - max, so a zero probability adds an exact zero and
+// huge logits give no NaN.  keep(col) is 1 - sum of the collected objects' p_terminate held to [0, 1], the env's own
+// behaviour (a bernoulli(p) with p >= 1 always terminates); the backward kernels follow the reference's DP and do
+// not clamp.
+__device__ __forceinline__ void occupancy_step(const OptretSetup& T, unsigned long long* da, int nxo, int pos, int e,
+                                               const float* l, double m, double (&acc)[OCC_SUMS],
+                                               unsigned long long* colsum) {
+  const int G2 = T.G2;
+  // the largest logit's action i1 and the second-largest's i2 (another maximum, if there is one), found on the f32
+  // logits: exp is monotone, so x[i1] = exp(0) = 1 is the largest x and x[i2] the second-largest
+  int i1 = 0;
+  float mx = l[0];
+#pragma unroll
+  for (int a = 1; a < 5; ++a)
+    if (l[a] > mx) { mx = l[a]; i1 = a; }
+  int i2 = i1 == 0 ? 1 : 0;
+  float m2 = i1 == 0 ? l[1] : l[0];
+#pragma unroll
+  for (int a = 1; a < 5; ++a)
+    if (a != i1 && l[a] > m2) { m2 = l[a]; i2 = a; }
+  double x[5], den = 0.0, xd = 0.0, sec = 0.0;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const double d = (double)l[a] - (double)mx;
+    x[a] = exp(d);
+    den += x[a];
+    xd += x[a] * d;
+    sec = a == i2 ? x[a] : sec;
+  }
+  const double inv = 1.0 / den;
+  acc[OCC_ENT] += m * (log(den) - xd * inv);
+  acc[OCC_LC] += m * (1.0 - inv);
+  acc[OCC_MM] += m * (1.0 - (inv - sec * inv));
+  const int absent = T.used & ~e;
+  const double* pwa = T.pw + absent * T.NE;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const uint32_t en = T.nxt[pos * 5 + a];
+    const int col = (int)(en >> 8) & e;
+    const double w = m * (x[a] * inv);
+    double keep = 1.0;
+    if (col != 0) {
+      const double r = T.rsum[col], kw = T.keepw[col];
+      keep = kw < 0.0 ? 0.0 : (kw > 1.0 ? 1.0 : kw);
+      acc[OCC_RET] += w * r;
+      acc[OCC_RABS] += w * fabs(r);
+      const unsigned long long ft = (unsigned long long)(w * (1.0 - keep) * kOccOne);
+      if (ft != 0) atomicAdd(colsum + TOUED_MAX_OBJS, ft);
+      const unsigned long long f = (unsigned long long)(w * kColOne);
+      for (int c = col; c != 0; c &= c - 1) atomicAdd(colsum + __builtin_ctz(c), f);
+    }
+    const double wk = w * keep;
+    if (!(wk > 0.0)) continue;
+    unsigned long long* dst = da + nxo + (int)(en & 0xFFu) + G2 * (e & ~col);   // an outcome adds G2 * R
+    int R = 0;
+    do {
+      const unsigned long long f = (unsigned long long)(wk * pwa[R] * kOccOne);
+      if (f != 0) atomicAdd(dst + G2 * R, f);
+      R = (R - absent) & absent;
+    } while (R != 0);
+  }
+}
+
+// State occupancy of a tabular agent's own policy, the forward counterpart of k_policy_return:
+//   d_0 = 1 at (start cell, all used objects present),   d_{t+1}(s') = sum_s d_t(s) sum_a pi_t(a|s) P(s' | s, a)
+// for t = 0 .. H-1, d_t(s) = P(the first episode is still running at step t and is in state s).  k_policy_return's
+// setup, work order, block size and theta rows in registers; the two LDS tables hold d_t and d_{t+1} as u64 fixed
+// point (occupancy_step).  A thread reads only its own entries of the current table and clears each right after
+// reading it, so the table is clean when it becomes the next step's target: one LDS barrier per step.  A state without
+// mass does no work, so the early steps cost what the reachable front contains.  Results are bit-identical from run
+// to run and do not depend on the other levels of the batch: the tables are integer sums, a thread's f64 sums run in
+// its own fixed order, and they are combined once, by a fixed tree (wave butterflies, then the waves in order).
+// Outputs (f32, one rounding each): summary[8] (toued.h), visits[s] = sum_t d_t(s) (0 at the invalid states),
+// collected[o] = the expected collections of object o, and the optional rows occ_all[t] = d_t, stored from the table
+// before the step clears it (one more barrier per step) with zero rows for t >= H.
+template <int ITEMS>
+__global__ __launch_bounds__(1024) void k_policy_occupancy(const int* __restrict__ levels,
+                                                           const float* __restrict__ theta, int D, int max_grid,
+                                                           int n_max, int L, float* __restrict__ summary,
+                                                           float* __restrict__ visits, float* __restrict__ collected,
+                                                           float* __restrict__ occ_all) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ double s_part[16][OCC_SUMS];      // a wave's sums; at most 16 waves
+  __shared__ double s_tot[OCC_SUMS];
+  __shared__ unsigned long long s_col[TOUED_MAX_OBJS + 1];      // collections; the early-termination mass
+  const OptretSetup T = optret_setup(smem, levels, max_grid, n_max, L, occ_all);
+  const int S = T.S, G2 = T.G2;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int nwork = T.ncell * T.ne;      // <= S <= ITEMS * blockDim (the host's choice of ITEMS)
+  unsigned long long* const da = reinterpret_cast<unsigned long long*>(T.va);
+  // both tables as fixed-point zeros (the setup's f64 fill has -inf at the invalid states), d_0 at the start state
+  const int start = T.lev[L_START] + G2 * T.used;
+  for (int s = tid; s < 2 * S; s += nt) da[s] = (s == start && T.H > 0) ? (1ull << 62) : 0ull;
+  if (tid <= TOUED_MAX_OBJS) s_col[tid] = 0ull;
+  float last[5], row[ITEMS][5];
+  int st[ITEMS];
+  policy_items(T, theta + (size_t)blockIdx.x * D * 5, D, nwork, last, st, row);
+  __syncthreads();
+
+  double acc[OCC_SUMS], vis[ITEMS];
+#pragma unroll
+  for (int i = 0; i < OCC_SUMS; ++i) acc[i] = 0.0;
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) vis[k] = 0.0;
+  int curo = 0;    // d_t, read and cleared
+  int nxo = S;     // d_{t+1}, added to
+  for (int t = 0; t < T.H; ++t) {
+    if (occ_all != nullptr) {
+      float* out = occ_all + ((size_t)blockIdx.x * L + t) * S;
+      for (int s = tid; s < S; s += nt) out[s] = (float)((double)da[curo + s] * kOccInv);
+      lds_barrier();      // the row is read before its entries' owners clear them
+    }
+    const float c = __fmul_rn((float)t, 0.001f);
+    float tl[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) tl[a] = __fmul_rn(c, last[a]);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      if (st[k] < 0) continue;
+      int sk = st[k];
+      asm volatile("" : "+v"(sk));      // as in k_policy_moments: what derives from the item is formed per step
+      const int pos = sk & 0xFF, e = sk >> 8;
+      const int si = curo + pos + G2 * e;
+      const unsigned long long u = da[si];
+      if (u == 0) continue;
+      da[si] = 0;
+      const double m = (double)u * kOccInv;
+      vis[k] += m;
+      float l[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) l[a] = __fadd_rn(row[k][a], tl[a]);
+      occupancy_step(T, da, nxo, pos, e, l, m, acc, s_col);
+    }
+    lds_barrier();
+    const int sw = curo; curo = nxo; nxo = sw;
+  }
+  // table curo holds d_H
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k)
+    if (st[k] >= 0) {
+      acc[OCC_ALIVE] += (double)da[curo + (st[k] & 0xFF) + G2 * (st[k] >> 8)] * kOccInv;
+      acc[OCC_LEN] += vis[k];
+    }
+
+  if (visits != nullptr) {
+    float* out = visits + (size_t)blockIdx.x * S;
+    const int g = T.lev[L_GRID], g2 = g * g;
+    for (int s = tid; s < S; s += nt) {      // the invalid states, which no thread owns
+      const int pos = s % G2, e = s / G2;
+      if (!(pos < g2 && !wall_at(T.lev, pos) && !(e & ~T.used))) out[s] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k)
+      if (st[k] >= 0) out[(st[k] & 0xFF) + G2 * (st[k] >> 8)] = (float)vis[k];
+  }
+
+  // the block's sums: a butterfly inside each wave, then the waves in order
+#pragma unroll
+  for (int i = 0; i < OCC_SUMS; ++i) {
+    double v = acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((tid & 63) == 0) s_part[tid >> 6][i] = v;
+  }
+  __syncthreads();
+  if (tid < OCC_SUMS) {
+    double v = 0.0;
+    for (int w = 0; w < (nt >> 6); ++w) v += s_part[w][tid];
+    s_tot[tid] = v;
+  }
+  __syncthreads();
+  if (tid < 8) {
+    const double len = s_tot[OCC_LEN];
+    double v = tid == OCC_PTERM ? (double)s_col[TOUED_MAX_OBJS] * kOccInv : s_tot[tid];
+    if (tid == OCC_ENT) v = len > 0.0 ? v / (len * log(5.0)) : 0.0;
+    if (tid == OCC_LC || tid == OCC_MM) v = len > 0.0 ? v / len : 0.0;
+    summary[(size_t)blockIdx.x * 8 + tid] = (float)v;
+  }
+  if (collected != nullptr && tid < n_max)
+    collected[(size_t)blockIdx.x * n_max + tid] = (float)((double)s_col[tid] * kColInv);
+}
+
 // Raises kernel K's dynamic-LDS limit on its first launch, then launches it: one workgroup of `block` threads per
 // level.  `who` is the entry point, for the messages.
 template <auto K, class... Args>
@@ -579,6 +786,25 @@ int toued_policy_return_moments(const int* levels, const float* theta, int n, in
   return by_items(items, [&](auto I) {
     return optret_launch<k_policy_moments<decltype(I)::value>>(who, n, block, lds, stream, levels, theta, D, max_grid,
                                                                n_max, max_rollout_len, v0, var0, v_all, var_all);
+  });
+}
+
+int toued_policy_occupancy(const int* levels, const float* theta, int n, int D, int max_grid, int n_max, int tabular,
+                           int max_rollout_len, float* summary, float* visits, float* collected, float* occ_all,
+                           hipStream_t stream) {
+  const char* const who = __func__;
+  size_t lds;
+  if (optret_check(who, tabular, n, max_rollout_len, max_grid, n_max, &D, optret_lds_bytes, &lds)) return -1;
+  if (n == 0) return 0;
+  TOUED_REQUIRE(summary != nullptr, "%s: summary is required", who);
+  // toued_policy_return's LDS, block size and items per thread; every mode's table has at most six
+  const int S = D - 1, block = optret_block(S), items = (S + block - 1) / block;
+  TOUED_REQUIRE(items <= 6, "%s: max_grid=%d n_max=%d has %d states per thread (limit 6)", who, max_grid, n_max,
+                items);
+  return by_items(items, [&](auto I) {
+    return optret_launch<k_policy_occupancy<decltype(I)::value>>(who, n, block, lds, stream, levels, theta, D,
+                                                                 max_grid, n_max, max_rollout_len, summary, visits,
+                                                                 collected, occ_all);
   });
 }
 

@@ -123,6 +123,7 @@ _SIGS = {
     "toued_optimal_return": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
     "toued_policy_return": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "toued_policy_return_moments": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "toued_policy_occupancy": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "toued_project_simplex": [_P, _P, _I, _I, _P, _P],
     "toued_nash_fits": [_I],
     "toued_nash_solve": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P],

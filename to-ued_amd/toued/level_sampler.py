@@ -19,7 +19,9 @@ level, kept per slot in ``LevelBuffer.max_return``; every env mode, not with
 ``min_margin`` (PLR with the mean over the agent's eval trajectory of its
 policy's entropy over log 5, of 1 - max pi, or of 1 - (max pi - second-largest
 pi): no critic, no antagonist, no buffer state; every env mode, also with
---use_es, not in the reference).
+--use_es, not in the reference; with ``--policy_score_eval exact``, tabular
+modes, the mean is over the exact state occupancy of the agent's policy on the
+level instead: no keys, no eval rollout, toued.plr.exact_policy_scores).
 Level editor (``--level_editor``; not in the reference): ``none``, or ``accel``:
 with probability ``--edit_prob`` a slot freed by ``_reset_lowest_scoring`` is
 refilled by ``--num_edits`` small edits (``--edit_ops``) of a high-scoring buffer
@@ -93,7 +95,8 @@ POLICY_SCORE_FUNCTIONS = score_family("policy")
 SCORE_TRANSFORMS = ["proportional", "rank", "rank_sampled"]
 TRANSFORM_CODES = {"rank": 0, "proportional": 1, "rank_sampled": 2}     # toued_plr_sample_prio's `transform`
 REGRET_EVALS = ("sampled", "exact")      # --regret_eval: eval rollouts, or RolloutWrapper.policy_return
-LEVEL_EDITORS = ("none", "accel")        # --level_editor: refill reset slots from the generator, or by ACCEL edits
+POLICY_SCORE_EVALS = ("sampled", "exact")      # --policy_score_eval: the eval trajectory, or policy_occupancy
+LEVEL_EDITORS = ("none", "accel")       # --level_editor: refill reset slots from the generator, or by ACCEL edits
 
 
 @dataclass
@@ -157,6 +160,15 @@ class LevelSampler:
                                                 and self.spec.tabular):
             raise ValueError(f"regret_eval exact needs score_function alg_regret or optimal_regret and a tabular "
                              f"environment mode (got {args.score_function}, {self.env_mode})")
+        self.policy_score_eval = getattr(args, "policy_score_eval", "sampled")
+        if self.policy_score_eval not in POLICY_SCORE_EVALS:
+            raise ValueError(f"policy_score_eval {self.policy_score_eval} not in {POLICY_SCORE_EVALS}")
+        if self.policy_score_eval == "exact" and not (needs.family == "policy" and self.spec.tabular):
+            raise ValueError(f"policy_score_eval exact needs score_function policy_entropy, least_confidence or "
+                             f"min_margin and a tabular environment mode (got {args.score_function}, {self.env_mode})")
+        if getattr(args, "occupancy_metrics", False) and not self.spec.tabular:
+            raise ValueError(f"occupancy_metrics needs a tabular environment mode: the agent is not a table over the "
+                             f"states of {self.env_mode}")
         level_editor = getattr(args, "level_editor", "none")
         if level_editor not in LEVEL_EDITORS:
             raise ValueError(f"level_editor {level_editor} not in {LEVEL_EDITORS}")

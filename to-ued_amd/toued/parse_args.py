@@ -24,6 +24,19 @@ Additions (all default to the reference's behaviour):
                         agent's eval trajectory of the policy entropy -sum_a pi log pi divided by log 5 (its maximum),
                         of the least confidence 1 - max_a pi, or of the min margin 1 - (max_a pi - second-largest_a pi).
                         No antagonist, no value critic (so also with --use_es), no buffer state; every env mode
+  --policy_score_eval {sampled,exact}  how the three policy scores average their per-state terms: ``sampled`` (the
+                        default) over the agent's eval trajectory, ``exact`` over the exact state occupancy of its
+                        policy on the level (RolloutWrapper.policy_occupancy): the per-step average over the first
+                        episode, which is the long-run per-step average of the sampled score, since the episodes of a
+                        tabular level are independent and identically distributed; the sampled score over T steps
+                        differs from it by the truncated last episode, an O(1/T) bias, and by sampling noise.  No
+                        keys, no eval rollout, also with --use_es; tabular modes and these three scores only
+  --occupancy_metrics   add an ``occupancy`` dict to every log line, from one policy_occupancy launch on the agents and
+                        their levels after the meta-step's sample, means over all agents: ``episode_len``,
+                        ``p_early_term``, ``exact_return``, ``collect_pos`` / ``collect_neg`` (the expected collections
+                        of objects with a positive / negative reward) and ``cell_coverage`` (exp of the entropy of the
+                        visits per cell over the number of reachable cells: in (0, 1], 1 for a uniform visitation).
+                        Tabular modes
   --level_editor {none,accel}  how the PLR scores' reset round refills a freed buffer slot: ``none`` (the default) by
                         the level generator, ``accel`` with probability --edit_prob by --num_edits small edits
                         (--edit_ops: walls, objects, start, rewards; a reward moves by at most --edit_reward_delta) of a
@@ -144,6 +157,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--regret_eval", type=str, choices=["sampled", "exact"], default="sampled",
                    help="alg_regret / optimal_regret: evaluate the agents by eval rollouts (sampled, the reference) or "
                         "by the exact expected return of their policies (exact: deterministic, no keys; tabular modes)")
+    p.add_argument("--policy_score_eval", type=str, choices=["sampled", "exact"], default="sampled",
+                   help="policy_entropy / least_confidence / min_margin: average the policy terms over the agent's "
+                        "eval trajectory (sampled), or over the exact state occupancy of its policy on the level "
+                        "(exact: deterministic, no keys, no eval rollout; tabular modes)")
+    p.add_argument("--occupancy_metrics", action="store_true",
+                   help="Log what the agents' exact state occupancy on their levels says each meta-step (an "
+                        "'occupancy' dict: episode length, early-termination probability, exact return, collections "
+                        "of positive and negative objects, cell coverage; tabular modes)")
     p.add_argument("--level_editor", type=str, choices=["none", "accel"], default="none",
                    help="How the reset round of the PLR scores refills a freed buffer slot: by the level generator "
                         "(none), or with probability --edit_prob by small edits of a high-scoring buffer level (accel)")

@@ -40,6 +40,11 @@ expected return of its policy (toued_policy_return) in place of the eval rollout
 deterministic and key-free, and ``alg_regret`` trains its antagonists on the same keys and returns
 V^pi(A2C) - V^pi(LPG).  The default, ``sampled``, is the code path above, bit for bit.
 
+With ``--policy_score_eval exact`` (tabular modes; not in the reference) the three policy scores average their terms
+over the exact state occupancy of the agent's policy on its level (toued_policy_occupancy) in place of the eval
+trajectory: ``exact_policy_scores``, deterministic and key-free, no eval rollout.  The default, ``sampled``, is the code
+path above, bit for bit; ``--regret_eval`` stays the regret scores' switch and refuses these.
+
 With ``--score_transform rank_sampled`` or ``--staleness_coeff`` > 0 (neither in the reference) step 4 is
 toued_plr_sample_prio: Prioritized Level Replay's replay distribution (Jiang et al. 2021, section 3), the mixture
 (1 - rho) P_S + rho P_C of a score part P_S (rank_sampled: weight rank^(-1/score_temperature) over the descending-score
@@ -312,9 +317,32 @@ def policy_scores(sampler, keys: torch.Tensor, levels: torch.Tensor, lpg_theta: 
     and no buffer state.  The keys, the eval trajectory and the chunking are ``value_loss_scores``', so the scored
     trajectory is the one the other scores use, and the chunking changes no bit.  An extension: the reference's
     LevelSampler has no such score."""
+    if getattr(sampler, "policy_score_eval", "sampled") == "exact":
+        return exact_policy_scores(sampler, levels, lpg_theta)
     ro = sampler.rollout_manager
     return _chunked_scores(sampler, keys, levels, lpg_theta, chunk_agents, 3,
                            lambda lo, hi, out: ro.policy_scores(out, lpg_theta[lo:hi].contiguous()))
+
+
+def exact_policy_scores(sampler, levels: torch.Tensor, lpg_theta: torch.Tensor):
+    """``policy_scores``' three scores of n tabular LPG agents without an eval rollout (``--policy_score_eval exact``):
+    (policy entropy, least confidence, min margin), f32 [n] each, the same per-state terms averaged over the exact
+    state occupancy of the agent's policy on its level over ``eval_rollout_len`` steps
+    (RolloutWrapper.policy_occupancy's ``entropy``, ``least_confidence`` and ``min_margin``, bit for bit), that is
+    over the steps of the agent's first episode, each weighted by the probability that the episode reaches it.
+
+    What it is next to the sampled score: the episodes of a tabular level are independent and identically
+    distributed (reset is deterministic, at the start cell with all objects present), so the per-step average over the
+    first episode is the long-run per-step average of the sampled score (the renewal-reward theorem).  The sampled
+    score over T = ``eval_rollout_len`` steps and ``env_workers`` workers differs from it by the truncated last
+    episode, an O(1/T) bias, and by sampling noise.  No keys, no antagonist, no value critic (so also with --use_es),
+    one launch, deterministic.  An extension: the reference's LevelSampler has no such score."""
+    if levels.shape[0] == 0:
+        z = torch.zeros(0, dtype=torch.float32, device=levels.device)
+        return z, z.clone(), z.clone()
+    ro = sampler.rollout_manager
+    occ = ro.policy_occupancy(levels, lpg_theta, ro.eval_rollout_len)
+    return occ.entropy, occ.least_confidence, occ.min_margin
 
 
 def policy_entropy(sampler, keys, levels, lpg_theta) -> torch.Tensor:

@@ -15,6 +15,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -35,6 +36,23 @@ class Transition:
     action: torch.Tensor
     reward: torch.Tensor
     done: torch.Tensor
+
+
+class PolicyOccupancy(NamedTuple):
+    """RolloutWrapper.policy_occupancy's result: toued_policy_occupancy's eight summary columns, f32 [n] each (views
+    of one [n, 8] tensor), then ``visits`` f32 [n, S], ``collected`` f32 [n, max_n_objs] and ``occ_all`` (None, or
+    f32 [n, max_rollout_len, S])."""
+    ret: torch.Tensor                 # sum d pi r = V^pi_0(start), policy_return's value from the other side
+    length: torch.Tensor              # the expected number of steps of the first episode
+    p_early_term: torch.Tensor        # the probability that it ends by termination, not by the time limit
+    alive_end: torch.Tensor           # the probability that it is still running after the last step
+    entropy: torch.Tensor             # mean over the visited steps of the policy's entropy over log 5
+    least_confidence: torch.Tensor    # ... of 1 - max pi
+    min_margin: torch.Tensor          # ... of 1 - (max pi - second-largest pi)
+    ret_abs: torch.Tensor             # sum d pi |r|, the error scale of ``ret``
+    visits: torch.Tensor
+    collected: torch.Tensor
+    occ_all: torch.Tensor | None
 
 
 def _check_transition(name: str, transition: Transition):
@@ -267,6 +285,40 @@ class RolloutWrapper:
         _lib.call("toued_" + name, _lib.ptr(levels), *th, n, *d, self.spec.max_grid_size, self.spec.max_n_objs,
                   int(self.spec.tabular), L, *map(_lib.ptr, v0), *map(_lib.ptr, v_all), _lib.stream_ptr())
         return v_all if return_all else v0
+
+    def policy_occupancy(self, levels: torch.Tensor, theta: torch.Tensor, max_rollout_len: int,
+                         return_all: bool = False) -> PolicyOccupancy:
+        """The exact state occupancy of tabular agents' own policies over ``max_rollout_len`` steps
+        (toued_policy_occupancy, one launch, no host synchronisation): d_t(s), the probability that the agent's first
+        episode is still running at step t and is in state s, pushed forward from the start state under
+        ``policy_return``'s policy, and what follows from it (``PolicyOccupancy``): the return from the other side,
+        the episode's expected length and how it ends, the three policy scores as averages over the visited steps,
+        every state's expected visits and every object's expected collections.  Deterministic, key-free, and a level's
+        result does not depend on its batch.  Not in the reference.
+
+        levels int32 [n, 80], theta f32 [n, obs_dim, 5] -> the summary fields f32 [n], ``visits`` f32 [n, S] with
+        S = obs_dim - 1 (0 at the invalid states), ``collected`` f32 [n, max_n_objs] and ``occ_all``, None or with
+        ``return_all`` f32 [n, max_rollout_len, S] (rows from max_steps_in_episode on are 0).  A single level [80]
+        with theta [obs_dim, 5] returns every field without the leading axis.  Non-tabular modes raise
+        NotImplementedError."""
+        if not self.spec.tabular:
+            raise NotImplementedError("Policy occupancy not implemented for non-tabular environments.")
+        if levels.dim() == 1:
+            out = self.policy_occupancy(levels.view(1, -1), theta.unsqueeze(0), max_rollout_len, return_all)
+            return PolicyOccupancy(*(None if o is None else o[0] for o in out))
+        n, L = levels.shape[0], int(max_rollout_len)
+        if tuple(theta.shape) != (n, self.obs_dim, 5) or theta.dtype != torch.float32 or theta.device != levels.device:
+            raise ValueError(f"policy_occupancy: theta {theta.dtype} {tuple(theta.shape)} on {theta.device}, expected "
+                             f"float32 {(n, self.obs_dim, 5)} on {levels.device}")
+        S, dev = self.obs_dim - 1, levels.device
+        summary = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+        visits = torch.zeros((n, S), dtype=torch.float32, device=dev)
+        collected = torch.zeros((n, self.spec.max_n_objs), dtype=torch.float32, device=dev)
+        occ_all = torch.empty((n, L, S), dtype=torch.float32, device=dev) if return_all else None
+        _lib.call("toued_policy_occupancy", _lib.ptr(levels), _lib.ptr(theta), n, self.obs_dim,
+                  self.spec.max_grid_size, self.spec.max_n_objs, int(self.spec.tabular), L, _lib.ptr(summary),
+                  _lib.ptr(visits), _lib.ptr(collected), _lib.ptr(occ_all), _lib.stream_ptr())
+        return PolicyOccupancy(*summary.unbind(dim=1), visits, collected, occ_all)
 
     def value_loss_scores(self, transition: Transition, vcrit: torch.Tensor, gamma: float, gae_lambda: float,
                           return_adv: bool = False):

@@ -98,7 +98,37 @@ class Trainer:
             metrics = {**metrics, "levels": self.level_metrics()}
         if getattr(self.args, "buffer_diversity", False):
             metrics = {**metrics, "buffer": self.buffer_diversity()}
+        if getattr(self.args, "occupancy_metrics", False):
+            metrics = {**metrics, "occupancy": self.occupancy_metrics()}
         return metrics
+
+    def occupancy_metrics(self):
+        """--occupancy_metrics: where the agents go on the levels they are on, from one
+        RolloutWrapper.policy_occupancy launch (the exact state occupancy of each agent's policy over the eval rollout
+        length) and one toued.env.level_stats launch, as 0-d device tensors, means over all agents: ``episode_len``,
+        the expected length of the first episode; ``p_early_term``, the probability that it ends by termination;
+        ``exact_return``; ``collect_pos`` / ``collect_neg``, the expected collections of objects with a positive /
+        negative reward; ``cell_coverage``, exp(entropy of the visits per cell, summed over the existence masks and
+        normalised) over the number of reachable cells: in (0, 1], 1 when the visitation is uniform over the reachable
+        cells, no threshold.  The ranks' shards are summed with all_reduce_sum (sums and the count).  Tabular modes."""
+        from .env import L_NOBJS, L_REW, level_stats
+        ro, spec = self.sampler.rollout_manager, self.sampler.spec
+        levels = self.agents.levels
+        occ = ro.policy_occupancy(levels, self.agents.theta, ro.eval_rollout_len)
+        n, n_max = levels.shape[0], spec.max_n_objs
+        used = torch.arange(n_max, device=levels.device)[None, :] < levels[:, L_NOBJS:L_NOBJS + 1]
+        rew = levels[:, L_REW:L_REW + n_max].contiguous().view(torch.float32)
+        col = occ.collected
+        cells = occ.visits.view(n, 1 << n_max, -1).sum(dim=1)
+        p = cells / cells.sum(dim=1, keepdim=True).clamp(min=1e-30)
+        ent = -torch.xlogy(p, p).sum(dim=1)
+        reach = level_stats(levels, spec).n_reach.to(torch.float32).clamp(min=1.0)
+        v = torch.stack([occ.length.sum(), occ.p_early_term.sum(), occ.ret.sum(),
+                         (col * (used & (rew > 0))).sum(), (col * (used & (rew < 0))).sum(),
+                         (torch.exp(ent) / reach).sum(), torch.full((), float(n), device=levels.device)])
+        self.world.all_reduce_sum(v)
+        return {"episode_len": v[0] / v[6], "p_early_term": v[1] / v[6], "exact_return": v[2] / v[6],
+                "collect_pos": v[3] / v[6], "collect_neg": v[4] / v[6], "cell_coverage": v[5] / v[6]}
 
     def buffer_diversity(self):
         """--buffer_diversity: how different the level buffer's levels are, from one toued.env.level_nearest launch of
