@@ -536,6 +536,18 @@ int toued_max_mc_scores(int N, int W, int T, int D, const float* vcrit, const in
  * is held to row D-1.  Any W, T >= 1; 2 <= D <= 7065 (the table is staged in LDS); W * T < 2^31. */
 int toued_policy_scores(int N, int W, int T, int D, const float* theta, const int* tidx, const int* ttime,
                         float* entropy, float* least_conf, float* min_margin, float* steps, hipStream_t stream);
+/* Episode statistics of N agents' train trajectories (trew / tdone [N][T][W], toued_rollout's layout), carried from
+ * call to call: the sampled learning curve of the meta-test.  run_ret / run_len [N][W] hold the undiscounted return
+ * and the length of each worker's unfinished episode; they are read and written, and the caller zeroes them at the
+ * start of a lifetime.  Per worker, first step first: run_ret = run_ret + r_t (f32, one rounding), run_len += 1; on
+ * done_t the episode (run_ret, run_len) is recorded and both are cleared.  stats [N][6] f64 is ADDED TO: episodes
+ * recorded in these T steps, sum of their returns, sum of their squared returns, sum of their lengths, sum of all
+ * rewards, steps (W * T).  run_ret and run_len are bit-exact with the sequential restatement, and one call on T1 + T2
+ * steps leaves the carry of a call on T1 steps followed by one on T2 steps; the sums are kept in f64 in a fixed order
+ * without atomics: deterministic, and agent a's row depends on agent a's data only.  Only trew and tdone are read.
+ * N == 0 returns 0 before any pointer is looked at.  Any W, T >= 1; W * T < 2^31. */
+int toued_episode_stats(int N, int W, int T, const float* trew, const uint8_t* tdone, float* run_ret, int* run_len,
+                        double* stats, hipStream_t stream);
 
 /* ---- LPG reverse-time GRU on MFMA (models/lpg.py:11-35, flax GRUCell) ---- */
 size_t toued_gru_packed_floats(int which);

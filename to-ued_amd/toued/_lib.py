@@ -80,6 +80,7 @@ _SIGS = {
     "toued_value_loss_scores": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
     "toued_max_mc_scores": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
     "toued_policy_scores": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "toued_episode_stats": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
     "toued_sort_keys2048": [_P, _P, _I, _I, _P],
     "toued_gru_bwd_fused_fits": [_I, _I],
     "toued_gru_bwd_fused_work_floats": [_I, _I],

@@ -67,6 +67,13 @@ Additions (all default to the reference's behaviour):
   --staleness_coeff RHO PLR's staleness mixture: the replay distribution becomes (1 - RHO) P_S + RHO P_C, P_S the
                         --score_transform's distribution and P_C proportional to the rounds since a slot was last
                         scored; 0 (the default) is the reference's behaviour, in [0, 1], not with random / frozen
+  --eval_every M        after every M-th meta-step rank 0 runs the meta-test (toued.evaluate.MetaTest) on the current
+                        LPG parameters (--use_es: the search mean): fresh agents on --eval_levels held-out levels of
+                        --eval_mode drawn from PRNGKey(--eval_seed) are trained for their whole lifetime by the frozen
+                        rule, and a ``meta_test`` dict (``final_normalised``, ``final_exact_return``, ``auc`` over
+                        --curve_points points, ``n_degenerate``) is added to that log line.  It has its own keys,
+                        buffers and RolloutWrapper: training with and without it is bit-identical.  0 (the default)
+                        never runs it; a negative M or a non-tabular --eval_mode is refused.  Not sharded over ranks
 """
 from __future__ import annotations
 
@@ -196,6 +203,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "them (train.py:52-57: the scan carry is never unpacked)")
     p.add_argument("--fix_value_critic", action="store_true",
                    help="Actually train the meta-gradient value critic (reference discards the update)")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="Run the meta-test (toued.evaluate) on the current LPG after every this many meta-steps and "
+                        "log it as a 'meta_test' dict (0: never; training itself is unchanged)")
+    p.add_argument("--eval_mode", type=str, default="mazes",
+                   help="eval_every: environment mode of the held-out levels (tabular modes)")
+    p.add_argument("--eval_levels", type=int, default=64, help="eval_every: number of held-out levels")
+    p.add_argument("--eval_seed", type=int, default=0,
+                   help="eval_every: PRNGKey of the held-out levels and of the evaluation's own keys")
+    p.add_argument("--curve_points", type=int, default=11,
+                   help="eval_every: points of the learning curve, evenly spaced over the agents' lifetime")
     return p
 
 
@@ -214,4 +231,15 @@ def parse_args(cmd_args=None):
         raise ValueError("--edit_min_distance filters the level editor's children: it needs --level_editor accel")
     if args.buffer_diversity and args.score_function == "random":
         raise ValueError("--buffer_diversity measures the level buffer: --score_function random has none")
+    if args.eval_every < 0:
+        raise ValueError(f"--eval_every {args.eval_every} is negative")
+    if args.eval_every:
+        from . import modes
+        kw = modes.ENV_MODE_KWARGS.get(args.eval_mode)
+        if kw is None or not kw["tabular"]:
+            raise ValueError(f"--eval_every needs a tabular --eval_mode: the exact returns the meta-test normalises "
+                             f"by are not defined for {args.eval_mode}")
+        if args.eval_levels < 1 or args.curve_points < 1:
+            raise ValueError(f"--eval_every needs --eval_levels >= 1 and --curve_points >= 1 (got {args.eval_levels}, "
+                             f"{args.curve_points})")
     return args

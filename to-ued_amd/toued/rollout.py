@@ -55,6 +55,24 @@ class PolicyOccupancy(NamedTuple):
     occ_all: torch.Tensor | None
 
 
+class EpisodeStats(NamedTuple):
+    """RolloutWrapper.episode_stats's result: toued_episode_stats's six columns, f64 [N] each (views of one [N, 6]
+    tensor, ``table``, which a later call can be given as ``out`` to go on adding to it)."""
+    episodes: torch.Tensor        # episodes completed
+    ret_sum: torch.Tensor         # sum of their undiscounted returns
+    ret_sq_sum: torch.Tensor      # sum of their squared returns
+    len_sum: torch.Tensor         # sum of their lengths
+    reward_sum: torch.Tensor      # sum of all rewards, finished episode or not
+    steps: torch.Tensor           # (worker, step) pairs seen
+
+    @property
+    def table(self) -> torch.Tensor:
+        e = self.episodes
+        if e.dim() == 1 and (e.shape[0] <= 1 or e.stride(0) == 6):      # a column of the [N, 6] table it came from
+            return e.as_strided((e.shape[0], 6), (6, 1), e.storage_offset())
+        return torch.stack(tuple(self), dim=1)
+
+
 def _check_transition(name: str, transition: Transition):
     """(N, T, W) of a trajectory that the score kernels read, its shapes checked against one another."""
     N, T, W = transition.reward.shape
@@ -389,6 +407,39 @@ class RolloutWrapper:
                   _lib.ptr(transition.obs_time), _lib.ptr(ent), _lib.ptr(lc), _lib.ptr(mm), _lib.ptr(steps),
                   _lib.stream_ptr())
         return (ent, lc, mm, steps) if return_steps else (ent, lc, mm)
+
+    def episode_stats(self, transition: Transition, carry=None, out=None):
+        """The episodes that N agents' workers complete in a train trajectory, tracked across calls
+        (toued_episode_stats, one launch, no host synchronisation): episodes do not end where a train rollout ends,
+        so ``carry`` = (run_ret f32 [N, W], run_len int32 [N, W]) holds every worker's unfinished episode, its
+        undiscounted return and its length.  None starts a lifetime (zeros); the carry given is updated in place and
+        returned.  ``out``: an ``EpisodeStats`` (or its f64 [N, 6] ``table``) to add to, so that a bucket of updates
+        accumulates without a torch op per update; None starts from zero.  Only reward and done are read.
+
+        Returns (EpisodeStats, carry).  The running return is an f32 sum in time order, so one call on T1 + T2 steps
+        leaves the carry of a call on T1 steps followed by one on T2 steps, bit for bit.  Not in the reference."""
+        N, T, W = transition.reward.shape
+        if transition.done.shape != (N, T, W):
+            raise ValueError(f"episode_stats: reward {tuple(transition.reward.shape)}, done "
+                             f"{tuple(transition.done.shape)}")
+        dev = transition.reward.device
+        if carry is None:
+            carry = (torch.zeros((N, W), dtype=torch.float32, device=dev),
+                     torch.zeros((N, W), dtype=torch.int32, device=dev))
+        run_ret, run_len = carry
+        if run_ret.shape != (N, W) or run_ret.dtype != torch.float32 or run_len.shape != (N, W) \
+                or run_len.dtype != torch.int32 or run_ret.device != dev or run_len.device != dev:
+            raise ValueError(f"episode_stats: carry {run_ret.dtype} {tuple(run_ret.shape)}, {run_len.dtype} "
+                             f"{tuple(run_len.shape)}, expected float32 and int32 {(N, W)} on {dev}")
+        table = out.table if isinstance(out, EpisodeStats) else out
+        if table is None:
+            table = torch.zeros((N, 6), dtype=torch.float64, device=dev)
+        elif table.shape != (N, 6) or table.dtype != torch.float64 or table.device != dev:
+            raise ValueError(f"episode_stats: out {table.dtype} {tuple(table.shape)} on {table.device}, expected "
+                             f"float64 {(N, 6)} on {dev}")
+        _lib.call("toued_episode_stats", N, W, T, _lib.ptr(transition.reward), _lib.ptr(transition.done),
+                  _lib.ptr(run_ret), _lib.ptr(run_len), _lib.ptr(table), _lib.stream_ptr())
+        return EpisodeStats(*table.unbind(dim=1)), (run_ret, run_len)
 
     def eval_returns(self, agent_keys: torch.Tensor, theta: torch.Tensor, levels: torch.Tensor,
                      state: torch.Tensor) -> torch.Tensor:

@@ -83,6 +83,9 @@ class Trainer:
         # the reference's lpg_train_step_fn (train.py:33, meta/meta.py:33-52) driving this instance
         self.train_state = LpgTrainState(self.eta, None if args.use_es else self.adam)
         self.train_step = make_lpg_train_step(args, self.sampler, n_local, self.world, sl, impl=self.step_fn)
+        self.meta_steps = 0           # meta-steps done (--eval_every)
+        self._eval_set = None         # --eval_every: the held-out levels, their sub-modes and the evaluation's rng
+        self.last_meta_test = None
 
     def meta_step(self):
         """_meta_train_loop (train.py:36-54): LPG update, then level_sampler.sample."""
@@ -100,7 +103,25 @@ class Trainer:
             metrics = {**metrics, "buffer": self.buffer_diversity()}
         if getattr(self.args, "occupancy_metrics", False):
             metrics = {**metrics, "occupancy": self.occupancy_metrics()}
+        self.meta_steps += 1
+        every = getattr(self.args, "eval_every", 0)
+        if every and self.meta_steps % every == 0 and self.world.rank == 0:
+            metrics = {**metrics, "meta_test": self.meta_test()}
         return metrics
+
+    def meta_test(self):
+        """--eval_every: the meta-test of the current LPG parameters (--use_es: the search mean) on the held-out
+        levels --eval_seed names (toued.evaluate): ``final_normalised``, ``final_exact_return``, ``auc`` and
+        ``n_degenerate`` as plain numbers.  The levels, the evaluation's keys, its buffers and its RolloutWrapper are
+        its own and the parameters are copied, so the training state is not touched.  One GPU: the caller's."""
+        from .evaluate import MetaTest, draw_levels
+        if self._eval_set is None:
+            self._eval_set = draw_levels(self.args.eval_mode, self.args.eval_levels, self.args.eval_seed, self.dev)
+        levels, sub, rng = self._eval_set
+        eta = self.step_fn.es.mean if self.args.use_es else self.eta
+        res = MetaTest(self.args, eta, self.dev).run(levels, rng, sub)
+        self.last_meta_test = res
+        return res.log_dict()
 
     def occupancy_metrics(self):
         """--occupancy_metrics: where the agents go on the levels they are on, from one
